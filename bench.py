@@ -2,7 +2,7 @@
 """bench.py -- ALS ratings/sec per full iteration, Netflix-shape k=64 fp32 on 1..8 MI355X (BASELINE.json).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload netflix|powerlaw] [--k 64|128]
-                  [--exchange native|torch] [--movie-chunks C]
+                  [--exchange native|torch] [--movie-chunks C] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,12 @@ ratings, inputs resident in HBM before the timed region:
 The dataset is fixed as N grows (strong scaling): users and movies are sharded by id % N, one process per GPU, and
 with N > 1 each process synthesizes only its shard's ratings (~2/N of them: als_dataset_synthetic_*_shard).
 
-Prints ONE JSON line (rank 0). `roofline` describes the dominant kernel launch (the slower of the two halves' fused
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times the K steps (ms_per_step = wall time of the timed
+loop / K), writes the factors of the last step with --dump-outputs DIR (DIR/U.npy, DIR/M.npy and the rows they hold
+in DIR/U_rows.npy, DIR/M_rows.npy; the inputs are seeded, so two builds run with the same arguments can be compared
+array for array) and prints the line; roofline, counters, cpu_baseline, mse_after, build and -- at N = 1 -- the
+integrity self-check are null there and filled in by --full:
+`roofline` describes the dominant kernel launch (the slower of the two halves' fused
 gather/Gram/solve launches; both are under roofline.per_launch), timed with HIP events on the stream the kernel is
 launched on, against the ceiling that binds it: the MFMA pipe (the Gram's MFMAs as issued against the dense
 bf16/f16 peak) or the gather of the opposite factor rows (bytes requested / time against the chip's gather ceiling
@@ -231,6 +236,29 @@ def load_counters(k, nnz, lib_sha, workload="netflix", shard_of=0, dev_sha=None)
                   f"{lib_sha[:12]} (device code {str(c.get('device_code_sha256'))[:12]} != {str(dev_sha)[:12]})")
 
 
+DUMP_TABLE_BYTES = 24 << 20   # per factor table; with the row lists both stay far below 64 MB
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(app, out_dir):
+    """--dump-outputs: the factor matrices after the last timed step as a caller of the timed path reads them
+    (ALSApp.factors(): rows in ascending id order), <name>.npy in float32 (float64 for an f64 engine) with the row
+    indices kept in <name>_rows.npy (float64, exact): the whole table, or -- above DUMP_TABLE_BYTES -- a row sample
+    drawn with a fixed seed, so that two builds run with the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    U, M = app.factors()
+    for si, (name, a) in enumerate((("U", U), ("M", M))):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        rows = np.arange(a.shape[0])
+        keep = DUMP_TABLE_BYTES // max(1, a.strides[0])
+        if a.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(DUMP_SEED + si).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -243,8 +271,17 @@ def main():
     ap.add_argument("--nnz", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0xA15)
     ap.add_argument("--lam", type=float, default=0.05)
-    ap.add_argument("--cpu-seconds", type=float, default=7.0, help="CPU baseline seconds per thread count")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the per-launch roofline with the profiled counters, the CPU "
+                         "baseline, the MSE after the last step, the replica / integrity self-check and the build "
+                         "record (a plain run sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the factors the last step left, as a caller reads them "
+                         "(ALSApp.factors(): U and M in ascending id order), to DIR/U.npy and DIR/M.npy with the rows "
+                         "kept in DIR/U_rows.npy and DIR/M_rows.npy (a seeded row sample of a table above "
+                         f"{DUMP_TABLE_BYTES >> 20} MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=7.0, help="--full: CPU baseline seconds per thread count")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline leg")
     ap.add_argument("--overlap-chunks", type=int, default=4, help="user-half chunks per all-gather overlap (N > 1)")
     ap.add_argument("--exchange", choices=("torch", "native"), default="native",
                     help="N > 1: all-gathers through the engine's own RCCL communicator behind the C ABI (default: "
@@ -352,14 +389,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:   # every rank holds full replicas of both factor matrices
+        dump_outputs(app, args.dump_outputs)
+
     # self-check of a sharded run: every rank's factor replicas bitwise equal, every integrity record clean
     # (CFK_BENCH_PERTURB_RANK=r: fault injection for tests/test_distributed.py -- rank r alters one word of its
-    # user-factor replica before the check)
+    # user-factor replica before the check); a one-process run checks its integrity record with --full only
     pr = os.environ.get("CFK_BENCH_PERTURB_RANK")
     if pr is not None and world > 1 and int(pr) == rank:
         app.engine.synchronize()
         app.engine.factors[1][0, 0] += 1.0
-    check = app.verify_replicas()
+    check = app.verify_replicas() if args.full or world > 1 else None
 
     # per-half device time over the timed steps (HIP events on the launch stream), per half-iteration: with the
     # chunked user half (N > 1) one half is several launches, summed here
@@ -369,11 +409,12 @@ def main():
     for side in ("movie", "user"):
         g, r, _ = eng.timing_collect(side)
         g_ms[side], r_ms[side] = g / K, r / K
-    mse = app.mse() if not solo else None   # a lone shard's factors are not a model
+    mse = app.mse() if args.full and not solo else None   # a lone shard's factors are not a model
 
-    if rank == 0:
+    info = {"movie": app.info[0], "user": app.info[1]}
+    build = roofline = cpu = None
+    if rank == 0 and args.full:
         build = build_record()
-        info = {"movie": app.info[0], "user": app.info[1]}
         ctr, ctr_why = (load_counters(args.k, nnz_total, build["lib_sha256"], args.workload,
                                       args.shard_of if solo else 0, build["device_code_sha256"])
                         if world == 1 else (None, "N > 1"))
@@ -494,11 +535,11 @@ def main():
                     "table exceeds the Infinity Cache); traffic = PMC FETCH_SIZE x2 + "
                     "WRITE_SIZE per launch; counters = rocprofv3 SQ passes of this build",
         }
-        cpu = None
         if world == 1 and not solo and not args.no_cpu_baseline:
             share, share_src = cpu_share()
             counts = [4] + ([share] if share != 4 else [])      # reference's stream threads, the box's share
             cpu = cpu_baseline(ds, args.k, args.lam, args.cpu_seconds, counts, share_src)
+    if rank == 0:
         # whole-job ratings per second; --shard-of: this rank's share (its in-block entries, averaged over the halves)
         shard_nnz = (info["movie"]["nnz"] + info["user"]["nnz"]) / 2
         value = (shard_nnz if solo else nnz_total) * K / elapsed
@@ -528,9 +569,11 @@ def main():
             "projection_note": ("this rank's rate x G: assumes balanced shards (id % G balances the Netflix shape; on the "
                                 "power-law workload the heaviest items make rank 0 the longest) and leaves out the "
                                 "exchange (DESIGN.md section 4)") if solo else None,
+            "full": bool(args.full), "dump_outputs": args.dump_outputs,
+            # None below: left to --full (mse_after, build, roofline, cpu_baseline; the self-check at N = 1)
             "mse_after": mse,
-            "replicas_agree": check["replicas_agree"], "integrity_clean": check["integrity_clean"],
-            "replica_digest": check["digest"],
+            "replicas_agree": check and check["replicas_agree"], "integrity_clean": check and check["integrity_clean"],
+            "replica_digest": check and check["digest"],
             "setup_s": t_setup,
             "build": build,
             "roofline": roofline,
@@ -539,7 +582,7 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
-    if not (check["replicas_agree"] and check["integrity_clean"]):
+    if check and not (check["replicas_agree"] and check["integrity_clean"]):
         print(f"bench: rank {rank}: self-check failed: replicas_agree={check['replicas_agree']} "
               f"integrity_clean={check['integrity_clean']} ({check['integrity_failures']} bad partial slots)",
               file=sys.stderr, flush=True)

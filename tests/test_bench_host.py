@@ -97,6 +97,32 @@ def test_bench_refuses_the_debug_library(tmp_path, copy):
     assert r.returncode != 0 and "refused" in r.stderr, r.stderr[-2000:]
 
 
+def test_dump_outputs_whole_tables_and_seeded_row_samples(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a table within the size cap is written whole, a larger one as the rows a fixed seed
+    draws (ascending, the same on every call), both as float32 with the row indices beside them"""
+    import numpy as np
+
+    class App:
+        def factors(self):
+            rng = np.random.default_rng(3)
+            return rng.random((1000, 64), dtype=np.float32), rng.random((37, 64), dtype=np.float32)
+
+    monkeypatch.setattr(bench, "DUMP_TABLE_BYTES", 100 * 64 * 4)
+    U, M = App().factors()
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(App(), str(tmp_path / d))
+        got.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("U", "U_rows", "M", "M_rows")})
+        assert sorted(os.listdir(tmp_path / d)) == ["M.npy", "M_rows.npy", "U.npy", "U_rows.npy"]
+    a, b = got
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert a["U"].dtype == np.float32 and a["M"].dtype == np.float32 and a["U_rows"].dtype == np.float64
+    assert np.array_equal(a["M"], M) and np.array_equal(a["M_rows"], np.arange(37))
+    rows = a["U_rows"].astype(np.int64)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and 0 <= rows[0] and rows[-1] < 1000
+    assert np.array_equal(a["U"], U[rows])
+
+
 def test_prof_summary_sums_the_chunk_launches_of_each_half(tmp_path, monkeypatch):
     """tools/prof_summary.py on a chunked run (bench config launches_per_half = 2 movie + 3 user launches per
     iteration): the trace summary and the per-half counters are sums over each half-iteration's launches, in dispatch

@@ -308,7 +308,7 @@ def test_bench_rehearsal_two_ranks_shard_restricted(tmp_path):
     port = s.getsockname()[1]
     s.close()
     common = ["--workload", "powerlaw", "--users", "20000", "--movies", "1500", "--nnz", "600000", "--steps", "3",
-              "--warmup", "1", "--no-cpu-baseline"]
+              "--warmup", "1", "--full", "--no-cpu-baseline"]   # --full: mse_after, build and the self-check
     env = dict(os.environ, OMP_NUM_THREADS="8")
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
@@ -336,3 +336,44 @@ def test_bench_rehearsal_two_ranks_shard_restricted(tmp_path):
     assert lb["replicas_agree"] is False and lb["integrity_clean"] is True
     if not os.environ.get("CFK_ALS_LIB"):   # the product library (an A/B variant carries no build stamp)
         assert l1["build"]["source_matches_tree"] and l1["build"]["binary_matches_tree"]
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path, cfk):
+    """A plain bench.py run (--gpus 1 --steps K --warmup W) at reduced size: the result line carries the headline
+    fields and leaves what only --full measures at null; --dump-outputs writes the factors after warmup + K
+    iterations -- bitwise those of ALSApp run here on the same seeded dataset (float32, both tables whole at this
+    size) -- and a --full run with the same arguments dumps the same arrays beside its extra records."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    shape, steps, warmup = (20_000, 1_500, 600_000), 2, 1
+    common = ["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--users", str(shape[0]),
+              "--movies", str(shape[1]), "--nnz", str(shape[2])]
+    lines, dumps = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        out = tmp_path / mode
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra +
+                           ["--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[mode] = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+        assert sorted(os.listdir(out)) == ["M.npy", "M_rows.npy", "U.npy", "U_rows.npy"]
+        dumps[mode] = {n[:-4]: np.load(out / n) for n in os.listdir(out)}
+    for mode, line in lines.items():
+        assert line["steps"] == steps and line["warmup"] == warmup and line["n_gpus"] == 1 and line["dtype"] == "f32"
+        assert line["unit"] == "ratings/s" and line["higher_is_better"] is True and line["ms_per_step"] > 0
+        assert abs(line["value"] - shape[2] / (line["ms_per_step"] / 1000.0)) <= 1e-9 * line["value"]
+        assert line["full"] is (mode == "full")
+    p, f = lines["plain"], lines["full"]
+    assert p["metric"] == f["metric"]
+    assert all(p[key] is None for key in ("roofline", "cpu_baseline", "build", "mse_after", "integrity_clean"))
+    assert f["roofline"]["per_launch"].keys() == {"movie", "user"} and f["build"]["lib_sha256"]
+    assert f["mse_after"] > 0 and f["integrity_clean"] is True and f["replicas_agree"] is True
+    ds = cfk.Dataset.synthetic_netflix(*shape, 0xA15, nthreads=min(16, os.cpu_count() or 1))
+    app = cfk.ALSApp(1, 64, LAM, steps, precision="f32", seed=42).setup(ds, check_duplicates=False)
+    app.run(warmup + steps)
+    U, M = app.factors()
+    for d in dumps.values():
+        assert d["U"].dtype == np.float32 and d["M"].dtype == np.float32
+        assert np.array_equal(d["U_rows"], np.arange(shape[0])) and np.array_equal(d["M_rows"], np.arange(len(M)))
+        assert np.array_equal(d["U"], U) and np.array_equal(d["M"], M)

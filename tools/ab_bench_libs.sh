@@ -1,6 +1,7 @@
 # bench.py A/B of two library builds on one box: "<build dir A>" "<build dir B>" [ROUNDS] [bench args...]
 set -u
 A=$1; B=$2; rounds=${3:-2}; shift 3
+set -- --full "$@"   # the per-launch times below are part of the --full line
 mkdir -p gpurun_out/ab_libs
 for r in $(seq 1 $rounds); do
     for v in "$A" "$B"; do

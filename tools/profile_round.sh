@@ -1,6 +1,6 @@
 #!/bin/bash
 # One round's measurement set on the GPU box, everything under gpurun_out/prof_<tag>/:
-#   bench.json            the default bench.py line (200 timed steps, CPU baseline included)
+#   bench.json            the bench.py --full line (200 timed steps; roofline, build record, CPU baseline included)
 #   trace/                rocprofv3 --kernel-trace --stats of a 20-step bench run (kernel_stats.csv)
 #   fetch/, write/        one PMC pass each: FETCH_SIZE, WRITE_SIZE (they cannot share a pass)
 #   lds/                  LDS counters (bank-conflict and LDS-array cycles, LDS issue stalls) of the full launches
@@ -27,7 +27,7 @@ step() {   # step <seconds> <log> <cmd...>
     echo "$(date +%T) rc=$rc $log" | tee -a "$O/steps.log"
     if [ $rc -ne 0 ]; then tail -n 20 "$O/$log"; exit 99; fi
 }
-step 300 bench.json python3 bench.py $*
+step 300 bench.json python3 bench.py --full $*
 step 300 trace.log rocprofv3 --kernel-trace --stats -d "$O/trace" -o run --output-format csv -- python3 "$R/bench.py" $B
 step 300 fetch.log rocprofv3 --pmc FETCH_SIZE -d "$O/fetch" -o run --output-format csv -- python3 "$R/bench.py" $P
 step 300 write.log rocprofv3 --pmc WRITE_SIZE -d "$O/write" -o run --output-format csv -- python3 "$R/bench.py" $P
