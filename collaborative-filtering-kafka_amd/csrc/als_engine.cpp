@@ -1,4 +1,4 @@
-// als_engine.cpp -- the C ABI of include/als.h: engine lifetime, in-block upload + work plan, factor
+// als_engine.cpp -- the C ABI of include/als.h: engine lifetime, in-block upload (its work plan: als_plan.h), factor
 // buffers, and the half-iteration launch. See include/als.h for the reference interface each entry
 // point replaces.
 #include <hip/hip_runtime.h>
@@ -65,9 +65,9 @@ struct Block {
     std::vector<int32_t> cdoff[3];
     Task* d_sq_tasks = nullptr;     // every FULL + PARTIAL task incl. the short rows (als_sq_error)
     int32_t n_sq = 0;
-    bool presplit = false;          // gather a pre-split (scaled fp16 h/m) copy of the opposite table
-    // interleaved split rows: rows longer than ilv_chunk entries, blocks permuted chunk-major
-    int64_t ilv_rows = 0, ilv_tasks = 0, ilv_chunk = 0;
+    cfk::BlockLayout layout;        // the layout the plan was built with (chunk lengths, XCD ranges, pre-split)
+    // interleaved split rows: rows longer than layout.ilv entries, blocks permuted chunk-major
+    int64_t ilv_rows = 0, ilv_tasks = 0;
     // chunk-major slot layout (als_set_row_layout): local row i -> factor row row_offset + (i / rows_per_chunk) *
     // chunk_stride + i % rows_per_chunk; rows_per_chunk = 0: row_offset + i
     int64_t rows_per_chunk = 0, chunk_stride = 0;
@@ -86,6 +86,28 @@ struct Factors {
     void* ptr = nullptr;
     int64_t n_rows = 0;
     bool owned = false;
+};
+
+// What the environment says, read once when an engine is created (read_environment below lists the variables).
+struct Settings {
+    cfk::PlanKnobs plan;            // ALS_INTERLEAVE, ALS_XCD_RANGES, ALS_PRESPLIT, ALS_DUAL, ALS_CHUNK (+ debug orders)
+    bool gram_f32 = false;          // ALS_GRAM=f32
+    bool force_valu = false;        // ALS_FORCE_VALU=1
+    // ALS_REFINE_MIN_PIVOT (cfk::SolveArgs): 0.45 keeps the worst per-row error ratio to the reference's own fp32
+    // path where always refining puts it (0.41, tools/refine_accuracy.py; 0.30 lets it reach 1.2), and skips the
+    // step for nearly every Netflix-shape row (k = 128 user half 17.7 -> 14.9 ms); > 1 always refines
+    float refine_min_pivot = 0.45f;
+    bool dual_side = true;          // ALS_DUAL_SIDE: entry-space launches on a side stream beside the main launch
+    int64_t comm_timeout_ms = 120000;   // ALS_COMM_TIMEOUT_S: bound of host waits while a communicator exists
+                                        // (als_comm_set_timeout)
+    // debug build only (CFK_DEBUG_KNOBS)
+    int32_t debug_flags = 0;        // ALS_DEBUG_SKIP_SOLVE / _REFINE
+    uint32_t debug_gen_skew = 0;    // ALS_DEBUG_REDUCE_GEN_SKEW=n, REDUCE decodes with generation + n (tests the
+                                    // integrity check: every slot reads as written by another launch)
+    int32_t debug_extra_lds = 0;    // ALS_DEBUG_EXTRA_LDS=bytes of unused LDS per main-launch workgroup (occupancy
+                                    // sweeps of the MFMA kernels)
+    bool debug_fixed_gen = false;   // ALS_DEBUG_FIXED_GEN=1, every launch uses generation 1, so partial slots of
+                                    // repeated launches are bitwise comparable (diagnostics)
 };
 
 }  // namespace
@@ -113,36 +135,18 @@ struct als_engine {
     size_t stage_bytes = 0;
     uint32_t* d_integrity = nullptr;   // cfk::INTEGRITY_WORDS: partial slots that failed their check
     int cu_count = 0;               // compute units of the device: the range guard's fallback grid
-    // ALS_INTERLEAVE: interleaved split rows + pre-split Gram for halves whose opposite table outgrows the L2s
-    // (-1 auto, 0 off, 1 wherever the pre-split Gram exists)
-    int interleave = -1;
-    // ALS_XCD_RANGES: an interleaved half's long rows are cut by opposite-slot range into 8 pieces whose chunks run on
-    // the XCD of that range (-1 auto: KP = 64 and an opposite table within 128 MiB, 0 off, 1 on)
-    int xcd_ranges = -1;
+    Settings cfg;                   // what the environment said when the engine was created (read_environment)
     uint32_t gen = 0;               // launch generation of the next PARTIAL/REDUCE pair
-    int32_t debug_flags = 0;        // debug build only (CFK_DEBUG_KNOBS): ALS_DEBUG_SKIP_SOLVE / _REFINE
-    uint32_t debug_gen_skew = 0;    // debug build only: ALS_DEBUG_REDUCE_GEN_SKEW=n, REDUCE decodes with generation
-                                    // + n (tests the integrity check: every slot reads as written by another launch)
-    // ALS_REFINE_MIN_PIVOT (cfk::SolveArgs): 0.45 keeps the worst per-row error ratio to the reference's own fp32
-    // path where always refining puts it (0.41, tools/refine_accuracy.py; 0.30 lets it reach 1.2), and skips the
-    // step for nearly every Netflix-shape row (k = 128 user half 17.7 -> 14.9 ms); > 1 always refines
-    float refine_min_pivot = 0.45f;
-    int32_t debug_extra_lds = 0;    // debug build only: ALS_DEBUG_EXTRA_LDS=bytes of unused LDS per main-launch
-                                    // workgroup (occupancy sweeps of the MFMA kernels)
-    bool debug_fixed_gen = false;   // debug build only: ALS_DEBUG_FIXED_GEN=1, every launch uses generation 1, so
-                                    // partial slots of repeated launches are bitwise comparable (diagnostics)
     ncclComm_t comm = nullptr;      // RCCL communicator over the G engines (one per GPU) of a sharded run
     int world = 1, rank = 0;
     hipStream_t comm_stream = nullptr;   // all-gathers run here, overlapping the next chunk's solve
     hipEvent_t solved = nullptr;         // recorded on `stream` before each all-gather
     hipEvent_t gathered[2] = {nullptr, nullptr};   // last all-gather of each side, on comm_stream
     bool gather_pending[2] = {false, false};
-    int64_t comm_timeout_ms = 120000;    // bound of host waits while a communicator exists (als_comm_set_timeout)
     int last_gather_side = -1;           // the last all-gather issued (for the timeout's message)
     int64_t last_gather_chunk = -1, last_gather_rows = 0;
     // Entry-space (als_solve_dual) launches run on side_stream, forked from and joined back into `stream`, so
-    // they fill the CUs the main launch's tail leaves idle (ALS_DUAL_SIDE=0: same stream, after the main launch)
-    bool dual_side = true;
+    // they fill the CUs the main launch's tail leaves idle (unless cfg.dual_side is off)
     hipStream_t side_stream = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
     bool timing = false;
@@ -158,9 +162,6 @@ int check_engine(const als_engine* e) {
     return ALS_OK;
 }
 
-// Drain the engine's stream and read the partial-slot integrity record (cfk::SlotCodec): a REDUCE task that
-// found a slot it could not see freshly written by this launch's PARTIAL task makes every later synchronising
-// call fail until als_integrity_status(..., reset = 1).
 // Order the engine's stream after the pending all-gathers of the given sides (comm_stream -> stream).
 int wait_gathers(als_engine* e, bool movie, bool user) {
     const bool want[2] = {movie, user};
@@ -175,7 +176,7 @@ int wait_gathers(als_engine* e, bool movie, bool user) {
 // Host wait for the engine's stream, bounded while the engine has a communicator: on expiry the communicator is
 // aborted (so that its kernels end) and the call fails naming the last all-gather issued.
 int stream_wait(als_engine* e, hipStream_t s) {
-    if (!e->comm || e->comm_timeout_ms <= 0) {
+    if (!e->comm || e->cfg.comm_timeout_ms <= 0) {
         HIP_TRY(hipStreamSynchronize(s));
         return ALS_OK;
     }
@@ -186,13 +187,13 @@ int stream_wait(als_engine* e, hipStream_t s) {
         if (st != hipErrorNotReady) return fail(ALS_ERR_DEVICE, "stream wait: %s", hipGetErrorString(st));
         const int64_t ms =
             std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-        if (ms > e->comm_timeout_ms) {
+        if (ms > e->cfg.comm_timeout_ms) {
             (void)ncclCommAbort(e->comm);
             e->comm = nullptr;
             return fail(ALS_ERR_COMM,
                         "rank %d of %d: the engine's stream did not complete within %lld ms; the last RCCL all-gather "
                         "issued was side %s chunk %lld (%lld rows per shard); communicator aborted",
-                        e->rank, e->world, (long long)e->comm_timeout_ms,
+                        e->rank, e->world, (long long)e->cfg.comm_timeout_ms,
                         e->last_gather_side == ALS_SIDE_MOVIE ? "movie" : e->last_gather_side == ALS_SIDE_USER ? "user"
                                                                                                               : "none",
                         (long long)e->last_gather_chunk, (long long)e->last_gather_rows);
@@ -202,6 +203,9 @@ int stream_wait(als_engine* e, hipStream_t s) {
     }
 }
 
+// Drain the engine's stream and read the partial-slot integrity record (cfk::SlotCodec): a REDUCE task that
+// found a slot it could not see freshly written by this launch's PARTIAL task makes every later synchronising
+// call fail until als_integrity_status(..., reset = 1).
 int sync_checked(als_engine* e) {
     if (int r = wait_gathers(e, true, true)) return r;
     if (int r = stream_wait(e, e->stream)) return r;
@@ -238,23 +242,73 @@ void free_block(Block& b) {
     b = Block();
 }
 
-// Chunk length (entries, multiple of 4) above which a row is split into PARTIAL tasks + a REDUCE task.
-// Aim for enough wave-tasks to fill 256 CUs several times over while keeping partial traffic small.
-int64_t chunk_entries(int64_t nnz_padded) {
-    constexpr int64_t B = cfk::BLOCK_ENTRIES;
-    if (const char* env = getenv("ALS_CHUNK")) {
-        long v = atol(env);
-        if (v >= 1) return (v + B - 1) / B * B;
+// The one place the library reads the environment: once per engine, in als_engine_create. A variable changed later
+// has no effect on that engine.
+//
+//   variable              values                                  default
+//   ALS_GRAM              f32: the exact-f32 MFMA Gram instead    split-MFMA Gram (fp32, k >= 32)
+//                         of the split one
+//   ALS_FORCE_VALU        1: the LDS-staged VALU Gram             off
+//   ALS_CHUNK             n >= 1: entries per contiguous chunk    nnz_padded / 4096 within [1024, 32768]
+//                         of a split row, rounded up to 32
+//   ALS_INTERLEAVE        0 off, else on wherever the pre-split   auto (opposite table of 32 MB .. 256 MiB, als_plan.cpp)
+//                         Gram exists
+//   ALS_XCD_RANGES        0 off, else on for interleaved halves   auto (KP = 64, opposite table within 128 MiB)
+//   ALS_PRESPLIT          1 on, anything else off                 auto (KP = 128, small or interleaved table)
+//   ALS_DUAL              0 off: no short rows in entry space     on (split path, KP = 64 / 128)
+//   ALS_DUAL_SIDE         0: entry-space launches on the main     side stream
+//                         stream
+//   ALS_REFINE_MIN_PIVOT  x: refine when a scaled pivot < x       0.45 (product build: never below 0.45)
+//   ALS_COMM_TIMEOUT_S    seconds (fraction allowed), <= 0 none   120
+// Debug build only (CFK_DEBUG_KNOBS, Makefile target `debug`; never in the product library):
+//   ALS_DEBUG_SKIP_SOLVE, ALS_DEBUG_SKIP_REFINE   1: drop the k x k solve / the refinement step
+//   ALS_DEBUG_REDUCE_GEN_SKEW   n: REDUCE decodes with generation + n       0
+//   ALS_DEBUG_FIXED_GEN         1: every launch uses generation 1           off
+//   ALS_DEBUG_EXTRA_LDS         bytes of unused LDS per workgroup           0
+//   ALS_ILV_CHUNK               n: interleave length (at least 32)          measured lengths (als_plan.cpp)
+//   ALS_TASK_ORDER              random | stagger[:W]: main-launch order     longest first
+Settings read_environment() {
+    Settings c;
+    if (const char* env = getenv("ALS_GRAM")) c.gram_f32 = !strcmp(env, "f32");
+    if (const char* env = getenv("ALS_FORCE_VALU")) c.force_valu = env[0] == '1';
+    if (const char* env = getenv("ALS_CHUNK")) c.plan.chunk = atol(env);
+    if (const char* env = getenv("ALS_INTERLEAVE")) c.plan.interleave = env[0] == '0' ? 0 : 1;
+    if (const char* env = getenv("ALS_XCD_RANGES")) c.plan.xcd_ranges = env[0] == '0' ? 0 : 1;
+    if (const char* env = getenv("ALS_PRESPLIT")) c.plan.presplit = env[0] == '1' ? 1 : 0;
+    if (const char* env = getenv("ALS_DUAL")) c.plan.dual = env[0] != '0';
+    if (const char* env = getenv("ALS_DUAL_SIDE")) c.dual_side = env[0] != '0';
+    if (const char* env = getenv("ALS_REFINE_MIN_PIVOT")) {
+        // the product library can only refine MORE often than the validated gate (> 1: every row); thresholds
+        // below 0.45 drop accuracy (tools/refine_accuracy.py) and are accepted by the debug build only
+        c.refine_min_pivot = (float)atof(env);
+#ifndef CFK_DEBUG_KNOBS
+        c.refine_min_pivot = std::max(c.refine_min_pivot, 0.45f);
+#endif
     }
-    // nnz/4096 (24.5k entries at Netflix shape; kbench: movie half + REDUCE 3.38 -> 3.19 ms against the
-    // former nnz/24576 <= 8192, fewer 11-KB partial slots and REDUCE solves), still nnz-proportional so a
-    // G-way shard keeps enough tasks for load balance
-    int64_t c = nnz_padded / 4096;
-    c = std::max<int64_t>(c, 1024);
-    c = std::min<int64_t>(c, 32768);
-    return (c + B - 1) / B * B;
+    if (const char* env = getenv("ALS_COMM_TIMEOUT_S")) c.comm_timeout_ms = (int64_t)(atof(env) * 1000.0);
+#ifdef CFK_DEBUG_KNOBS
+    // work-dropping diagnostics: compiled only into the tools' debug build, never into the product library
+    if (const char* env = getenv("ALS_DEBUG_SKIP_SOLVE"))
+        if (env[0] == '1') c.debug_flags |= cfk::SOLVE_FLAG_SKIP_SOLVE;
+    if (const char* env = getenv("ALS_DEBUG_SKIP_REFINE"))
+        if (env[0] == '1') c.debug_flags |= cfk::SOLVE_FLAG_SKIP_REFINE;
+    // integrity fault injection / slot-level diagnostics (tests/test_gpu_integrity.py, tools/split_diag.py): they
+    // weaken the partial-slot check, so they exist in the debug build only
+    if (const char* env = getenv("ALS_DEBUG_REDUCE_GEN_SKEW")) c.debug_gen_skew = (uint32_t)atoi(env);
+    if (const char* env = getenv("ALS_DEBUG_FIXED_GEN")) c.debug_fixed_gen = env[0] == '1';
+    if (const char* env = getenv("ALS_DEBUG_EXTRA_LDS")) c.debug_extra_lds = atoi(env);
+    // measurement knobs of the plan
+    if (const char* env = getenv("ALS_ILV_CHUNK")) c.plan.ilv_chunk = std::max(32L, atol(env));
+    if (const char* env = getenv("ALS_TASK_ORDER")) {
+        if (std::strncmp(env, "stagger", 7) == 0) {
+            c.plan.task_order = cfk::PlanKnobs::STAGGER;
+            if (env[7] == ':') c.plan.stagger_window = std::max(1, atoi(env + 8));
+        }
+        if (std::strcmp(env, "random") == 0) c.plan.task_order = cfk::PlanKnobs::RANDOM;
+    }
+#endif
+    return c;
 }
-
 }  // namespace
 
 extern "C" {
@@ -297,11 +351,9 @@ int als_engine_create(int device, int num_features, int precision, als_engine** 
     // small k use the LDS-staged VALU Gram. fp32 Gram products via the exact split (Path::MFMA_SPLIT) by default;
     // ALS_GRAM=f32 selects the v_mfma_f32_16x16x4_f32 path (same accumulator layout, 2.3x the Gram time).
     Path path = generic ? Path::GENERIC : (precision == ALS_F32 && num_features >= 32) ? Path::MFMA_SPLIT : Path::VALU;
-    if (path == Path::MFMA_SPLIT)
-        if (const char* env = getenv("ALS_GRAM"))
-            if (!strcmp(env, "f32")) path = Path::MFMA;
-    if (const char* env = getenv("ALS_FORCE_VALU"))
-        if (env[0] == '1' && !generic) path = Path::VALU;
+    const Settings cfg = read_environment();
+    if (path == Path::MFMA_SPLIT && cfg.gram_f32) path = Path::MFMA;
+    if (cfg.force_valu && !generic) path = Path::VALU;
     if (!cfk::variant_available(precision, kp, path))
         return fail(ALS_ERR_UNSUPPORTED, "no kernel variant for precision=%d kp=%d", precision, kp);
     int ndev = 0;
@@ -314,31 +366,7 @@ int als_engine_create(int device, int num_features, int precision, als_engine** 
     e->kp = kp;
     e->precision = precision;
     e->path = path;
-#ifdef CFK_DEBUG_KNOBS
-    // work-dropping diagnostics: compiled only into the tools' debug build (Makefile target `debug`), never into
-    // the product library
-    if (const char* env = getenv("ALS_DEBUG_SKIP_SOLVE"))
-        if (env[0] == '1') e->debug_flags |= cfk::SOLVE_FLAG_SKIP_SOLVE;
-    if (const char* env = getenv("ALS_DEBUG_SKIP_REFINE"))
-        if (env[0] == '1') e->debug_flags |= cfk::SOLVE_FLAG_SKIP_REFINE;
-    // integrity fault injection / slot-level diagnostics (tests/test_gpu_integrity.py, tools/split_diag.py): they
-    // weaken the partial-slot check, so they exist in the debug build only
-    if (const char* env = getenv("ALS_DEBUG_REDUCE_GEN_SKEW")) e->debug_gen_skew = (uint32_t)atoi(env);
-    if (const char* env = getenv("ALS_DEBUG_FIXED_GEN")) e->debug_fixed_gen = env[0] == '1';
-    if (const char* env = getenv("ALS_DEBUG_EXTRA_LDS")) e->debug_extra_lds = atoi(env);
-#endif
-    if (const char* env = getenv("ALS_REFINE_MIN_PIVOT")) {
-        // the product library can only refine MORE often than the validated gate (> 1: every row); thresholds
-        // below 0.45 drop accuracy (tools/refine_accuracy.py) and are accepted by the debug build only
-        e->refine_min_pivot = (float)atof(env);
-#ifndef CFK_DEBUG_KNOBS
-        e->refine_min_pivot = std::max(e->refine_min_pivot, 0.45f);
-#endif
-    }
-    if (const char* env = getenv("ALS_DUAL_SIDE")) e->dual_side = env[0] != '0';
-    if (const char* env = getenv("ALS_INTERLEAVE")) e->interleave = env[0] == '0' ? 0 : 1;
-    if (const char* env = getenv("ALS_XCD_RANGES")) e->xcd_ranges = env[0] == '0' ? 0 : 1;
-    if (const char* env = getenv("ALS_COMM_TIMEOUT_S")) e->comm_timeout_ms = (int64_t)(atof(env) * 1000.0);
+    e->cfg = cfg;
     hipError_t st = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (st != hipSuccess) {
         delete e;
@@ -450,56 +478,25 @@ int check_block_shape(als_engine* e, int64_t n_rows, int64_t row_offset, int64_t
 // Padded entries of a row of degree d (every row starts on a 32-entry block).
 inline int64_t padded(int64_t d) { return (d + cfk::BLOCK_ENTRIES - 1) / cfk::BLOCK_ENTRIES * cfk::BLOCK_ENTRIES; }
 
-// Interleaved split rows: on a half whose opposite table outgrows the L2s but fits the Infinity
-// Cache (the 123 / 246 MB user table of the Netflix-shape movie half at k = 64 / 128, the 256 MB item table of the
-// power-law user half), a row longer than the returned length (entries) is split into
-// nc = ceil(d / length) chunks of INTERLEAVED blocks -- chunk c = blocks c, c + nc, c + 2 nc, ... of the row -- so
-// that every chunk covers the row's whole range of opposite slots. With the chunks dispatched together (longest
-// first) the waves of an XCD then walk the opposite table in step and find its rows in their L2. Such a half gathers
-// the pre-split table (the fp16 Gram). 0: contiguous chunks at chunk_entries() (the other halves).
-int64_t interleave_chunk(const als_engine* e, int64_t n_opp_rows, const std::vector<int64_t>& deg) {
-    const int64_t sb = (n_opp_rows + 1) * (int64_t)cfk::presplit_row_bytes(e->kp);
-    if (e->interleave == 0 || e->path != Path::MFMA_SPLIT || (e->kp != 64 && e->kp != 128)) return 0;
-    if (n_opp_rows + 1 >= (1 << 24) || sb > (int64_t)UINT32_MAX) return 0;   // the pre-split gather's offsets
-    // auto: a table the L2s cannot hold (> 32 MB) that the 256 MiB Infinity Cache still holds; beyond the IC (configs[4]'s
-    // 2.56 GB user table) the contiguous chunks read the long rows' near-dense user ranges in order and win (item half
-    // of the power-law shard: 8.87 vs 14.6 ms interleaved, profiles/r06a)
-    if (e->interleave < 0 && (sb <= (32ll << 20) || sb > (256ll << 20))) return 0;
-    auto long_work = [&](int64_t t) {   // entries in rows longer than t
-        int64_t w = 0;
-        for (int64_t d : deg) w += d > t ? d : 0;
-        return w;
-    };
-    // the walk in step needs many chunks in flight: resident waves of the pre-split launch (4 per SIMD at KP = 64, 1 at
-    // KP = 128). Chunk length (kbench, Netflix shape, movie half + its REDUCE, profiles/r06a): k = 64, whole data:
-    // 8,192 / 10,240 / 12,288 / 16,384 / 24,576 entries 2.07 / 2.04 / 2.06 / 2.16 / 2.29 ms (contiguous chunks: 2.98);
-    // one rank's shard of G = 2 / 4 / 8 (fewer chunks than twice the resident waves): 1.52 / 0.95 / 0.66 ms at the
-    // best length vs 1.58 / 0.90 / 0.47 contiguous -- so k = 64 interleaves only with >= 1.5 x the resident waves of
-    // chunks. k = 128 (whole data 4,096 / 8,192 / 16,384: 5.76 / 5.32 / 5.06 ms, contiguous 6.67; shards of G = 2 / 4
-    // / 8 at 8,192: 4.92 / 2.55 / 1.37 vs 5.25 / 2.77 / 1.50) always. Round 6 (profiles/r06c/xcd2_*.log, movie half +
-    // REDUCE): whole data 16,384 / 8,192 / 4,096: 5.07 / 5.26 / 5.71 ms; shards of G = 2 / 4 / 8 at 4,096: 4.17 / 2.36 /
-    // ~1.40 ms vs 4.98 / 2.57 / 1.39 at 8,192 (2,048: 4.13 / 2.29 / 1.40; its REDUCE launch doubles) -- so 16,384 when
-    // the long rows hold over ~4 chunks of it per resident wave (the whole Netflix shape), else 4,096.
-    const int64_t conc = (int64_t)std::max(1, e->cu_count) * (e->kp == 128 ? 4 : 16);
-    int64_t len;
-    if (e->kp == 64) {
-        len = 10240;
-        // the concurrency rule holds for the 123 MB user table of a Netflix shard; the 256 MB item table of the
-        // power-law shard's user half interleaves whatever its long-row work (9.43 -> 7.38 ms, profiles/r06a; the rule
-        // alone had turned it off again: 9.47-9.57 ms, profiles/r06c/ranges_bench_ab)
-        if (e->interleave < 0 && sb <= (128ll << 20) && long_work(len) < len * conc * 3 / 2) return 0;
-    } else {
-        len = long_work(16384) >= 16384 * 4 * conc ? 16384 : 4096;
+// Replace the device copy *dst of a task list (nullptr for an empty list).
+int upload_tasks(Task** dst, const std::vector<Task>& src) {
+    if (*dst) {
+        (void)hipFree(*dst);
+        *dst = nullptr;
     }
-#ifdef CFK_DEBUG_KNOBS
-    if (const char* v = getenv("ALS_ILV_CHUNK")) len = std::max(32L, atol(v));
-#endif
-    return (len + cfk::BLOCK_ENTRIES - 1) / cfk::BLOCK_ENTRIES * cfk::BLOCK_ENTRIES;
+    const size_t bytes = src.size() * sizeof(Task);
+    if (bytes == 0) return ALS_OK;
+    hipError_t st = hipMalloc((void**)dst, bytes);
+    if (st != hipSuccess) return fail(ALS_ERR_OUT_OF_MEMORY, "hipMalloc(%zu): %s", bytes, hipGetErrorString(st));
+    st = hipMemcpy(*dst, src.data(), bytes, hipMemcpyHostToDevice);
+    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "hipMemcpy: %s", hipGetErrorString(st));
+    return ALS_OK;
 }
 
-// Work plan of a block whose padded in-block (d_col / d_rat, device, already laid out) has row degrees deg[]
-// and row starts begin[]: FULL / PARTIAL / REDUCE tasks, longest first; uploads the plan, takes ownership of
-// d_col / d_rat and sizes the partial and pre-split workspaces.
+// The device side of a block whose padded in-block (d_col / d_rat, device, already laid out) has row degrees deg[]
+// and row starts begin[]: plans it (als_plan.h: layout, then the task lists), permutes the interleaved rows' blocks,
+// packs the pre-split operands, uploads the plan, takes ownership of d_col / d_rat and sizes the partial and pre-split
+// workspaces.
 int finish_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, int64_t n_opp_rows, int64_t nnz,
                  const std::vector<int64_t>& deg, const std::vector<int64_t>& begin, int32_t* d_col, float* d_rat) {
     const int64_t nnz_padded = begin[n_rows];
@@ -507,33 +504,15 @@ int finish_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, in
         (void)hipFree(d_col);
         (void)hipFree(d_rat);
     };
-    // the generic path's workgroup takes a whole row of any length: no split rows
-    const int64_t chunk = e->path == Path::GENERIC ? INT64_MAX : chunk_entries(nnz_padded);
-    std::vector<Task> tasks, reduce, stasks;
-    int64_t slots = 0;
-    // Interleaved split rows: the long rows' blocks are permuted chunk-major (chunk c = blocks c, c + nc, ... of the
-    // row, in order), each chunk one PARTIAL task of whole blocks (the row's last, padded block is the last block of
-    // its chunk, so nent counts exactly the chunk's real entries), one REDUCE per row.
-    // (no longer than the contiguous chunk: a small block keeps enough tasks for load balance)
-    const int64_t ilv = std::min(interleave_chunk(e, n_opp_rows, deg), chunk);
-    std::vector<int32_t> perm;
-    std::vector<int8_t> srange;   // XCD range of each interleaved chunk task (ranges only)
-    int64_t ilv_rows = 0;
-    // XCD ranges (ALS_XCD_RANGES): a long row's blocks are first grouped by the opposite slot of their first entry
-    // into X = 8 ranges of the opposite table (a row's entries ascend by slot, so each range is a run of its blocks),
-    // then each range's blocks are interleaved into chunks as below. Chunk tasks of range x all run on one XCD (the
-    // task order below), so that XCD's L2 serves 1/8 of the table instead of every XCD fetching all of it.
-    // Measured (profiles/r06c/ranges_*.log): the k = 64 Netflix-shape movie half (123 MB user table, one launch) 2.00
-    // -> 1.80 ms, iteration 4.73 -> 4.60 ms; the k = 128 movie half (246 MB) and the power-law shard's chunked item-table
-    // half (256 MB) a little slower, shards of G = 2 / 4 slower than their contiguous plan -- so auto = KP = 64 with an
-    // opposite table within 128 MiB (each XCD's range within 16 MiB).
-    constexpr int XR = 8;
-    const bool ranges = ilv > 0 && n_opp_rows > 0 &&
-                        (e->xcd_ranges > 0 ||
-                         (e->xcd_ranges < 0 && e->kp == 64 &&
-                          (n_opp_rows + 1) * (int64_t)cfk::presplit_row_bytes(e->kp) <= (128ll << 20)));
+    cfk::BlockShape shape;
+    shape.path = e->path;
+    shape.k = e->k;
+    shape.kp = e->kp;
+    shape.cu_count = e->cu_count;
+    shape.n_opp_rows = n_opp_rows;
+    const cfk::BlockLayout layout = cfk::plan_layout(e->cfg.plan, shape, deg);
     std::vector<int32_t> bfirst;   // opposite slot of every block's first entry (physical position 0 of the block)
-    if (ranges && nnz_padded > 0) {
+    if (layout.ranges && nnz_padded > 0) {
         bfirst.resize((size_t)(nnz_padded / cfk::BLOCK_ENTRIES));
         hipError_t st = hipMemcpy2D(bfirst.data(), 4, d_col, cfk::BLOCK_ENTRIES * 4, 4, bfirst.size(),
                                     hipMemcpyDeviceToHost);
@@ -542,214 +521,24 @@ int finish_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, in
             return fail(ALS_ERR_DEVICE, "set_block: block heads: %s", hipGetErrorString(st));
         }
     }
-    if (ilv > 0) {
-        constexpr int64_t BE = cfk::BLOCK_ENTRIES;
-        std::vector<int64_t> piece[XR];
-        for (int64_t i = 0; i < n_rows; ++i) {
-            const int64_t d = deg[i];
-            if (d <= ilv) continue;
-            if (perm.empty()) {
-                perm.resize((size_t)(nnz_padded / BE));
-                for (size_t q = 0; q < perm.size(); ++q) perm[q] = (int32_t)q;
-            }
-            ++ilv_rows;
-            const int64_t nb = (d + BE - 1) / BE, b0 = begin[i] / BE;
-            for (auto& v : piece) v.clear();
-            for (int64_t q = 0; q < nb; ++q) {
-                const int x = ranges ? (int)std::min<int64_t>(XR - 1, (int64_t)bfirst[(size_t)(b0 + q)] * XR / n_opp_rows)
-                                     : 0;
-                piece[x].push_back(q);
-            }
-            Task t{};
-            t.row = (int32_t)i;
-            t.ndeg = (int32_t)d;
-            t.kind = cfk::TASK_PARTIAL;
-            const int64_t first = slots;
-            int64_t pos = 0;
-            for (int x = 0; x < XR; ++x) {
-                const std::vector<int64_t>& pb = piece[x];
-                if (pb.empty()) continue;
-                const int64_t np = (int64_t)pb.size();
-                const bool has_last = pb.back() == nb - 1;   // the row's padded block: last of its chunk below
-                const int64_t pent = BE * np - (has_last ? BE * nb - d : 0);
-                const int64_t nc = (pent + ilv - 1) / ilv;
-                for (int64_t c = 0; c < nc; ++c) {
-                    const int64_t p0 = pos;
-                    bool last = false;
-                    for (int64_t y = c; y < np; y += nc) {
-                        perm[(size_t)(b0 + pos++)] = (int32_t)(b0 + pb[(size_t)y]);
-                        last = pb[(size_t)y] == nb - 1;
-                    }
-                    const int64_t cnt = pos - p0;
-                    const int64_t nent = last ? BE * (cnt - 1) + (d - BE * (nb - 1)) : BE * cnt;
-                    Task p = t;
-                    p.begin = begin[i] + BE * p0;
-                    p.nent = (int32_t)nent;
-                    p.nsteps = (int32_t)((nent + 3) / 4);
-                    p.slot = (int32_t)slots++;
-                    stasks.push_back(p);
-                    srange.push_back((int8_t)x);
-                }
-            }
-            Task r = t;
-            r.begin = 0;
-            r.slot = (int32_t)first;
-            r.nsteps = (int32_t)(slots - first);
-            r.kind = cfk::TASK_REDUCE;
-            reduce.push_back(r);
-        }
-    }
-    const int64_t ilv_tasks = (int64_t)stasks.size();
-    for (int64_t i = 0; i < n_rows; ++i) {
-        if (ilv > 0 && deg[i] > ilv) continue;   // interleaved above
-        const int64_t d = deg[i];
-        Task t{};
-        t.row = (int32_t)i;
-        t.ndeg = (int32_t)d;
-        if (d <= chunk) {
-            t.begin = begin[i];
-            t.nsteps = (int32_t)((d + 3) / 4);
-            t.nent = (int32_t)d;
-            t.slot = -1;
-            t.kind = cfk::TASK_FULL;
-            tasks.push_back(t);
-        } else {
-            const int64_t first = slots;
-            for (int64_t o = 0; o < d; o += chunk) {
-                Task p = t;
-                p.begin = begin[i] + o;
-                p.nsteps = (int32_t)((std::min(chunk, d - o) + 3) / 4);
-                p.nent = (int32_t)std::min(chunk, d - o);
-                p.slot = (int32_t)slots++;
-                p.kind = cfk::TASK_PARTIAL;
-                tasks.push_back(p);
-            }
-            Task r = t;
-            r.begin = 0;
-            r.slot = (int32_t)first;
-            r.nsteps = (int32_t)(slots - first);
-            r.kind = cfk::TASK_REDUCE;
-            reduce.push_back(r);
-        }
-    }
-    // Short rows in entry space (split-bf16 path): rows of <= 3 blocks at KP = 128, 1 block at KP = 64 solve the
-    // (padded entries)^2 system of als_solve_dual instead of the KP x KP one. Only rows with n <= k entries: then
-    // Y Y^T + lambda n I_n has the nonzero spectrum of Y^T Y + lambda n I_k plus nothing smaller, so the same
-    // conditioning; with n > k the n x n system would carry n - k eigenvalues lambda n only (singular at
-    // lambda = 0 where the reference's k x k system is not). ALS_DUAL=0 turns it off.
-    std::vector<Task> sq_all = stasks;
-    sq_all.insert(sq_all.end(), tasks.begin(), tasks.end());
-    std::vector<Task> dual[3];
-    {
-        const int max_cd = e->path != Path::MFMA_SPLIT ? 0 : e->kp == 128 ? 6 : e->kp == 64 ? 2 : 0;
-        bool on = max_cd > 0;
-        if (const char* env = getenv("ALS_DUAL")) on = on && env[0] != '0';
-        if (on) {
-            std::vector<Task> keep;
-            for (const Task& t : tasks) {
-                const int cd = 2 * ((t.nent + cfk::BLOCK_ENTRIES - 1) / cfk::BLOCK_ENTRIES);
-                if (t.kind == cfk::TASK_FULL && t.ndeg > 0 && t.ndeg <= e->k && cd <= max_cd)
-                    dual[cd / 2 - 1].push_back(t);
-                else
-                    keep.push_back(t);
-            }
-            tasks.swap(keep);
-        }
-    }
-    if (slots > INT32_MAX || tasks.size() > (size_t)INT32_MAX) {
+    cfk::BlockPlan plan = cfk::plan_build(e->cfg.plan, shape, layout, deg, begin, bfirst);
+    if (plan.error) {
         drop();
-        return fail(ALS_ERR_UNSUPPORTED, "too many tasks / partial slots");
-    }
-    // Longest tasks first (LPT): the grid drains with a short tail.
-    std::stable_sort(tasks.begin(), tasks.end(), [](const Task& a, const Task& b) { return a.nsteps > b.nsteps; });
-#ifdef CFK_DEBUG_KNOBS
-    // ALS_TASK_ORDER=random / stagger[:W] (measurement knobs, debug build only): a seeded shuffle of the main launch's
-    // tasks, or LPT windows alternating between its longer and shorter half
-    if (const char* env = getenv("ALS_TASK_ORDER")) {
-        if (std::strncmp(env, "stagger", 7) == 0) {
-            // windows of W tasks (W = stagger:<W>, default 1024 = one 4-wave workgroup per CU) alternate between the
-            // longer and the shorter half of the LPT list: co-resident waves of a CU run tasks of different lengths
-            const size_t W = env[7] == ':' ? (size_t)std::max(1, atoi(env + 8)) : 1024;
-            const size_t h = (tasks.size() + 1) / 2;
-            std::vector<Task> out;
-            out.reserve(tasks.size());
-            size_t ia = 0, ib = h;
-            while (ia < h || ib < tasks.size()) {
-                for (size_t q = 0; q < W && ia < h; ++q) out.push_back(tasks[ia++]);
-                for (size_t q = 0; q < W && ib < tasks.size(); ++q) out.push_back(tasks[ib++]);
-            }
-            tasks.swap(out);
-        }
-        if (std::strcmp(env, "random") == 0) {
-            uint64_t x = 0x9e3779b97f4a7c15ull;
-            for (size_t i = tasks.size(); i > 1; --i) {
-                x ^= x << 13;
-                x ^= x >> 7;
-                x ^= x << 17;
-                std::swap(tasks[i - 1], tasks[(size_t)(x % i)]);
-            }
-        }
-    }
-#endif
-    std::stable_sort(reduce.begin(), reduce.end(), [](const Task& a, const Task& b) { return a.nsteps > b.nsteps; });
-    for (auto& d : dual)
-        std::stable_sort(d.begin(), d.end(), [](const Task& a, const Task& b) { return a.nsteps > b.nsteps; });
-
-    // the interleaved chunks join the plain tasks, longest first
-    if (!stasks.empty() && ranges) {
-        // XCD ranges: workgroup w runs on the XCD of w % 8 (round-robin placement; speed only, never correctness), so
-        // the workgroups at positions w = 8 j + x take range x's chunk tasks (queue x). The plain (whole-row) tasks have
-        // no range: each goes, longest first, to the queue of least work among those still short of an equal share of
-        // the task count, so the queues stay aligned to the round-robin. Every queue is longest first.
-        std::vector<Task> q[XR];
-        int64_t work[XR] = {};
-        for (size_t t = 0; t < stasks.size(); ++t) {
-            q[srange[t]].push_back(stasks[t]);
-            work[srange[t]] += stasks[t].nsteps;
-        }
-        const int64_t total = (int64_t)(stasks.size() + tasks.size());
-        const int64_t wgs = (total + 3) / 4;
-        for (const Task& t : tasks) {   // already longest first
-            int best = -1;
-            for (int x = 0; x < XR; ++x) {
-                const int64_t cap = 4 * ((wgs - x + XR - 1) / XR);   // tasks of the workgroups at w = x mod 8
-                if ((int64_t)q[x].size() < cap && (best < 0 || work[x] < work[best])) best = x;
-            }
-            if (best < 0) best = (int)(std::min_element(work, work + XR) - work);
-            q[best].push_back(t);
-            work[best] += t.nsteps;
-        }
-        std::vector<Task> out;
-        out.reserve((size_t)total);
-        for (int x = 0; x < XR; ++x)
-            std::stable_sort(q[x].begin(), q[x].end(), [](const Task& a, const Task& b) { return a.nsteps > b.nsteps; });
-        for (size_t j = 0;; j += 4) {
-            bool any = false;
-            for (int x = 0; x < XR; ++x)
-                for (size_t u = j; u < j + 4 && u < q[x].size(); ++u) {
-                    out.push_back(q[x][u]);
-                    any = true;
-                }
-            if (!any) break;
-        }
-        tasks.swap(out);
-    } else if (!stasks.empty()) {
-        tasks.insert(tasks.begin(), stasks.begin(), stasks.end());
-        std::stable_sort(tasks.begin(), tasks.end(), [](const Task& a, const Task& b) { return a.nsteps > b.nsteps; });
+        return fail(ALS_ERR_UNSUPPORTED, "%s", plan.error);
     }
 
     hipError_t st0 = hipSetDevice(e->device);
     if (st0 == hipSuccess) st0 = hipStreamSynchronize(e->stream);
-    if (st0 == hipSuccess && !perm.empty()) {
+    if (st0 == hipSuccess && !plan.perm.empty()) {
         // the long rows' blocks chunk-major (before the pre-split packing below derives its arrays from them)
         int32_t *d_perm = nullptr, *col2 = nullptr;
         float* rat2 = nullptr;
-        st0 = hipMalloc((void**)&d_perm, perm.size() * 4);
+        st0 = hipMalloc((void**)&d_perm, plan.perm.size() * 4);
         if (st0 == hipSuccess) st0 = hipMalloc((void**)&col2, (size_t)nnz_padded * 4);
         if (st0 == hipSuccess) st0 = hipMalloc((void**)&rat2, (size_t)nnz_padded * 4);
-        if (st0 == hipSuccess) st0 = hipMemcpy(d_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice);
+        if (st0 == hipSuccess) st0 = hipMemcpy(d_perm, plan.perm.data(), plan.perm.size() * 4, hipMemcpyHostToDevice);
         if (st0 == hipSuccess)
-            st0 = cfk::launch_permute_blocks(d_col, d_rat, col2, rat2, d_perm, (int64_t)perm.size(), nullptr);
+            st0 = cfk::launch_permute_blocks(d_col, d_rat, col2, rat2, d_perm, (int64_t)plan.perm.size(), nullptr);
         if (st0 == hipSuccess) st0 = hipDeviceSynchronize();
         (void)hipFree(d_perm);
         if (st0 == hipSuccess) {
@@ -772,26 +561,16 @@ int finish_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, in
     blk.n_opp_rows = n_opp_rows;
     blk.nnz = nnz;
     blk.nnz_padded = nnz_padded;
-    blk.n_tasks = (int32_t)tasks.size();
-    blk.n_reduce = (int32_t)reduce.size();
-    blk.n_slots = (int32_t)slots;
-    // Pre-split opposite table (scaled two-term fp16, cfk::launch_presplit, once per half) for the MFMA Gram: 4 KP
-    // bytes per row (the fp32 row's size), 3 MFMAs per tile instead of the on-the-fly bf16 split's 6, no split VALU
-    // (the rows reach LDS by DMA and the MFMA operands come back with transposed reads). Chosen where the Gram is
-    // MFMA-bound: always at KP = 128, and at KP = 64 for a cache-resident opposite table (<= 8 MB: the 17,770-row
-    // movie table of the user half, 2.99 vs 4.37 ms). The KP = 64 movie half gathers the 123 MB user table at the
-    // Infinity-Cache ceiling either way, and the split pass over that table would cost more than it saves (3.08 vs
-    // 3.01 ms; kbench). ALS_PRESPLIT=0/1 forces it off/on.
-    {
+    blk.layout = layout;
+    blk.n_tasks = (int32_t)plan.tasks.size();
+    blk.n_reduce = (int32_t)plan.reduce.size();
+    blk.n_slots = (int32_t)plan.slots;
+    blk.ilv_rows = plan.ilv_rows;
+    blk.ilv_tasks = plan.ilv_tasks;
+    if (layout.presplit) {
+        // the pre-split copy of the opposite table (cfk::launch_presplit, once per half), sized for the larger side
         const int64_t sb = (n_opp_rows + 1) * (int64_t)cfk::presplit_row_bytes(e->kp);
-        const bool ps_kp = e->path == Path::MFMA_SPLIT && (e->kp == 64 || e->kp == 128);
-        bool ps = ps_kp && (e->kp == 128 || sb <= (8ll << 20) || ilv > 0);
-        if (const char* env = getenv("ALS_PRESPLIT")) ps = ps_kp && env[0] == '1';
-        // the pre-split gather forms 32-bit byte offsets row * presplit_row_bytes with a 24-bit multiply: both the
-        // row (< 2^24) and the offset (< 2^32) must fit, also when ALS_PRESPLIT=1 forces the path
-        if (n_opp_rows + 1 >= (1 << 24) || sb > (int64_t)UINT32_MAX) ps = false;
-        blk.presplit = ps;
-        if (ps && (size_t)sb > e->split_bytes) {
+        if ((size_t)sb > e->split_bytes) {
             (void)hipFree(e->d_split);
             e->d_split = nullptr;
             e->split_bytes = 0;
@@ -800,7 +579,7 @@ int finish_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, in
                                               hipGetErrorString(st));
             e->split_bytes = (size_t)sb;
         }
-        if (ps && nnz_padded > 0) {
+        if (nnz_padded > 0) {
             // the RHS operand's ratings, packed once (setup time): fp16 rh pairs, then rm pairs
             hipError_t st = hipMalloc((void**)&blk.d_rat_pk, (size_t)nnz_padded * 4);
             if (st != hipSuccess) return fail(ALS_ERR_OUT_OF_MEMORY, "hipMalloc(%lld): %s", (long long)nnz_padded * 4,
@@ -813,33 +592,21 @@ int finish_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, in
             if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "pack ratings: %s", hipGetErrorString(st));
         }
     }
-    auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-        if (bytes == 0) return ALS_OK;
-        hipError_t st = hipMalloc(dst, bytes);
-        if (st != hipSuccess) return fail(ALS_ERR_OUT_OF_MEMORY, "hipMalloc(%zu): %s", bytes, hipGetErrorString(st));
-        st = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "hipMemcpy: %s", hipGetErrorString(st));
-        return ALS_OK;
-    };
-    int r;
-    if ((r = up((void**)&blk.d_tasks, tasks.data(), tasks.size() * sizeof(Task)))) return r;
-    blk.ilv_rows = ilv_rows;
-    blk.ilv_tasks = ilv_tasks;
-    blk.ilv_chunk = ilv;
-    if ((r = up((void**)&blk.d_reduce, reduce.data(), reduce.size() * sizeof(Task)))) return r;
+    if (int r = upload_tasks(&blk.d_tasks, plan.tasks)) return r;
+    if (int r = upload_tasks(&blk.d_reduce, plan.reduce)) return r;
     for (int c = 0; c < 3; ++c) {
-        if ((r = up((void**)&blk.d_dual[c], dual[c].data(), dual[c].size() * sizeof(Task)))) return r;
-        blk.n_dual[c] = (int32_t)dual[c].size();
-        blk.h_dual[c] = std::move(dual[c]);
+        if (int r = upload_tasks(&blk.d_dual[c], plan.dual[c])) return r;
+        blk.n_dual[c] = (int32_t)plan.dual[c].size();
+        blk.h_dual[c] = std::move(plan.dual[c]);
     }
-    if ((r = up((void**)&blk.d_sq_tasks, sq_all.data(), sq_all.size() * sizeof(Task)))) return r;
-    blk.n_sq = (int32_t)sq_all.size();
-    if (!sq_all.empty()) HIP_TRY(hipMalloc((void**)&blk.d_task_se, sq_all.size() * sizeof(double)));
-    blk.h_tasks = std::move(tasks);
-    blk.h_reduce = std::move(reduce);
+    if (int r = upload_tasks(&blk.d_sq_tasks, plan.sq_all)) return r;
+    blk.n_sq = (int32_t)plan.sq_all.size();
+    if (blk.n_sq > 0) HIP_TRY(hipMalloc((void**)&blk.d_task_se, plan.sq_all.size() * sizeof(double)));
+    blk.h_tasks = std::move(plan.tasks);
+    blk.h_reduce = std::move(plan.reduce);
     // Partial workspace sized for the larger side (the generic path: its per-workgroup Gram slabs, when the packed
     // triangle does not fit in LDS -- up to 1024 workgroups within 4 GiB)
-    size_t need = (size_t)slots * cfk::partial_words_per_lane(e->precision, e->kp, e->path) * 64 * e->elem();
+    size_t need = (size_t)plan.slots * cfk::partial_words_per_lane(e->precision, e->kp, e->path) * 64 * e->elem();
     if (e->path == Path::GENERIC) {
         const cfk::GenericPlan gp = cfk::generic_plan(e->precision, e->kp);
         if (!gp.g_in_lds) {
@@ -1084,12 +851,12 @@ int launch_half(als_engine* e, int side, float lambda, const Task* tasks, int32_
     a.scratch_slabs = e->generic_slabs;
     a.lambda = lambda;
     a.sentinel = (int32_t)b.n_opp_rows;
-    a.flags = e->path == Path::VALU ? 0 : e->debug_flags;
+    a.flags = e->path == Path::VALU ? 0 : e->cfg.debug_flags;
     if (++e->gen == 0) e->gen = 1;
-    a.gen = e->debug_fixed_gen ? 1u : e->gen;
+    a.gen = e->cfg.debug_fixed_gen ? 1u : e->gen;
     a.integrity = e->d_integrity;
-    a.refine_min_pivot = e->refine_min_pivot;
-    a.extra_lds = e->debug_extra_lds;
+    a.refine_min_pivot = e->cfg.refine_min_pivot;
+    a.extra_lds = e->cfg.debug_extra_lds;
     TimingRec rec{side, {nullptr, nullptr, nullptr}};
     if (e->timing) {
         for (auto& ev : rec.ev) {
@@ -1103,7 +870,7 @@ int launch_half(als_engine* e, int side, float lambda, const Task* tasks, int32_
         HIP_TRY(hipEventRecord(rec.ev[0], e->stream));
     }
     const bool any_dual = dl.n[0] > 0 || dl.n[1] > 0 || dl.n[2] > 0;
-    const bool side_dual = any_dual && e->dual_side;
+    const bool side_dual = any_dual && e->cfg.dual_side;
     if (side_dual) {   // the dual launches read the fp32 opposite table only: fork before the pre-split
         if (!e->side_stream) {
             HIP_TRY(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
@@ -1112,7 +879,7 @@ int launch_half(als_engine* e, int side, float lambda, const Task* tasks, int32_
         }
         HIP_TRY(hipEventRecord(e->fork, e->stream));
     }
-    if (b.presplit) {
+    if (b.layout.presplit) {
         // the opposite replica is the half's input and does not change between its chunks (als.h): chunk 0
         // converts it, later chunks reuse the conversion
         if (first_chunk) {
@@ -1127,8 +894,8 @@ int launch_half(als_engine* e, int side, float lambda, const Task* tasks, int32_
         a.col_ps = b.d_col_ps;
         a.amax = e->d_amax;
     }
-    HIP_TRY(cfk::launch_solve(e->precision, e->kp, e->path, a, e->stream, b.presplit, false));
-    if (b.presplit) {
+    HIP_TRY(cfk::launch_solve(e->precision, e->kp, e->path, a, e->stream, b.layout.presplit, false));
+    if (b.layout.presplit) {
         // the range guard's fallback: the same tasks on the fp32 table with the on-the-fly split, a launch whose
         // waves exit at once unless the opposite table is out of the pre-split's range (cfk::presplit_ok)
         cfk::SolveArgs f = a;
@@ -1152,7 +919,7 @@ int launch_half(als_engine* e, int side, float lambda, const Task* tasks, int32_
     if (n_reduce > 0) {
         a.tasks = reduce;
         a.n_tasks = n_reduce;
-        a.gen += e->debug_gen_skew;
+        a.gen += e->cfg.debug_gen_skew;
         HIP_TRY(cfk::launch_solve(e->precision, e->kp, e->path, a, e->stream, false, true));
     }
     if (e->timing) {
@@ -1187,45 +954,17 @@ int als_set_chunks(als_engine* e, int side, int n_chunks, const int64_t* row_bou
         return fail(ALS_ERR_INVALID_ARGUMENT, "row_bounds must run from 0 to n_rows (%lld)", (long long)b.n_rows);
     for (int c = 0; c < n_chunks; ++c)
         if (row_bounds[c + 1] < row_bounds[c]) return fail(ALS_ERR_INVALID_ARGUMENT, "row_bounds not monotone");
-    auto chunk_of = [&](int32_t row) {
-        return (int)(std::upper_bound(row_bounds, row_bounds + n_chunks + 1, (int64_t)row) - row_bounds) - 1;
-    };
     // stable partition by chunk keeps the longest-first order inside every chunk
-    auto split = [&](const std::vector<Task>& in, std::vector<Task>& out, std::vector<int32_t>& off) {
-        std::vector<std::vector<Task>> per(n_chunks);
-        for (const Task& t : in) per[chunk_of(t.row)].push_back(t);
-        off.assign(n_chunks + 1, 0);
-        out.clear();
-        for (int c = 0; c < n_chunks; ++c) {
-            out.insert(out.end(), per[c].begin(), per[c].end());
-            off[c + 1] = (int32_t)out.size();
-        }
-    };
     std::vector<Task> ct, cr, cdl[3];
-    split(b.h_tasks, ct, b.coff);
-    split(b.h_reduce, cr, b.croff);
-    for (int c = 0; c < 3; ++c) split(b.h_dual[c], cdl[c], b.cdoff[c]);
+    cfk::partition_by_chunk(b.h_tasks, n_chunks, row_bounds, ct, b.coff);
+    cfk::partition_by_chunk(b.h_reduce, n_chunks, row_bounds, cr, b.croff);
+    for (int c = 0; c < 3; ++c) cfk::partition_by_chunk(b.h_dual[c], n_chunks, row_bounds, cdl[c], b.cdoff[c]);
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    (void)hipFree(b.d_ctasks);
-    (void)hipFree(b.d_creduce);
-    b.d_ctasks = b.d_creduce = nullptr;
-    if (!ct.empty()) {
-        HIP_TRY(hipMalloc((void**)&b.d_ctasks, ct.size() * sizeof(Task)));
-        HIP_TRY(hipMemcpy(b.d_ctasks, ct.data(), ct.size() * sizeof(Task), hipMemcpyHostToDevice));
-    }
-    if (!cr.empty()) {
-        HIP_TRY(hipMalloc((void**)&b.d_creduce, cr.size() * sizeof(Task)));
-        HIP_TRY(hipMemcpy(b.d_creduce, cr.data(), cr.size() * sizeof(Task), hipMemcpyHostToDevice));
-    }
-    for (int c = 0; c < 3; ++c) {
-        (void)hipFree(b.d_cdual[c]);
-        b.d_cdual[c] = nullptr;
-        if (!cdl[c].empty()) {
-            HIP_TRY(hipMalloc((void**)&b.d_cdual[c], cdl[c].size() * sizeof(Task)));
-            HIP_TRY(hipMemcpy(b.d_cdual[c], cdl[c].data(), cdl[c].size() * sizeof(Task), hipMemcpyHostToDevice));
-        }
-    }
+    if (int r = upload_tasks(&b.d_ctasks, ct)) return r;
+    if (int r = upload_tasks(&b.d_creduce, cr)) return r;
+    for (int c = 0; c < 3; ++c)
+        if (int r = upload_tasks(&b.d_cdual[c], cdl[c])) return r;
     return ALS_OK;
 }
 
@@ -1541,7 +1280,7 @@ int als_comm_wait(als_engine* e) {
 
 int als_comm_set_timeout(als_engine* e, int64_t timeout_ms) {
     if (int r = check_engine(e)) return r;
-    e->comm_timeout_ms = timeout_ms;
+    e->cfg.comm_timeout_ms = timeout_ms;
     return ALS_OK;
 }
 
@@ -1550,8 +1289,8 @@ int als_block_path(const als_engine* e, int side, int* gram_path, int* presplit,
     if (int r = check_side(side)) return r;
     const Block& b = e->blk[side];
     if (gram_path) *gram_path = (int)e->path;
-    if (presplit) *presplit = b.presplit ? 1 : 0;
-    if (chunk) *chunk = b.set ? chunk_entries(b.nnz_padded) : 0;
+    if (presplit) *presplit = b.layout.presplit ? 1 : 0;
+    if (chunk) *chunk = b.set ? b.layout.chunk : 0;
     if (n_dual_rows)
         for (int c = 0; c < 3; ++c) n_dual_rows[c] = b.n_dual[c];
     return ALS_OK;
@@ -1574,8 +1313,8 @@ int als_block_split_info(const als_engine* e, int side, int64_t info[4]) {
     const Block& b = e->blk[side];
     info[0] = b.ilv_rows;
     info[1] = b.ilv_tasks;
-    info[2] = b.ilv_chunk;
-    info[3] = b.presplit ? 1 : 0;
+    info[2] = b.layout.ilv;
+    info[3] = b.layout.presplit ? 1 : 0;
     return ALS_OK;
 }
 

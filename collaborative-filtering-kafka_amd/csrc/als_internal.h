@@ -6,41 +6,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include "als_plan.h"   // Task, Path, the block layout constants: the HIP-free part
+
 namespace cfk {
-
-// One wave-sized unit of work of a half-iteration (host-built once per uploaded block, README.md:146-147:
-// the rating blocks never change, so the work plan is fixed for every iteration).
-//   kind FULL    : gather rows [begin, begin + 4*nsteps) of the padded in-block, accumulate Gram + RHS,
-//                  regularise, Cholesky-solve, store factor row `row`.
-//   kind PARTIAL : same gather/accumulate over one chunk of a long row; store the raw per-lane
-//                  accumulators into partial slot `slot` (no solve).
-//   kind REDUCE  : sum partial slots [slot, slot + nsteps) of row `row` in fixed order, then solve + store.
-enum TaskKind : int32_t { TASK_FULL = 0, TASK_PARTIAL = 1, TASK_REDUCE = 2 };
-
-// Device in-block layout: each row is padded to whole blocks of BLOCK_ENTRIES = 32 entries; padding entries
-// hold col = n_opp_rows (the sentinel zero row kept after the last factor row) and rating 0, so they add
-// nothing and need no masking in the kernels. Entry e of a
-// row is consumed by sub-step t = e / 4 (one MFMA K=4 step) in lane group g = e % 4; inside a block the
-// entries are stored group-major ([g][t], t < 8) so that one lane fetches the column indices of its 8
-// sub-steps with two 16-byte loads.
-constexpr int BLOCK_SUBSTEPS = 8;
-constexpr int BLOCK_ENTRIES = 4 * BLOCK_SUBSTEPS;
-__host__ __device__ constexpr int64_t block_position(int64_t e) {
-    const int64_t blk = e / BLOCK_ENTRIES, w = e % BLOCK_ENTRIES;
-    return blk * BLOCK_ENTRIES + (w % 4) * BLOCK_SUBSTEPS + w / 4;
-}
-
-struct alignas(16) Task {
-    int64_t begin;   // entry offset into the padded col/rating arrays (multiple of BLOCK_ENTRIES)
-    int32_t nsteps;  // FULL/PARTIAL: sub-steps holding real entries (ceil(n/4)); the task spans
-                     // ceil(nsteps / BLOCK_SUBSTEPS) blocks. REDUCE: number of partial slots
-    int32_t row;     // local row of the block (factor row = row_offset + row)
-    int32_t slot;    // PARTIAL: slot written; REDUCE: first slot read; FULL: -1
-    int32_t ndeg;    // true in-block size n_j (lambda * n_j * I, MFeatureCalculator.java:92-95)
-    int32_t kind;
-    int32_t nent;    // FULL/PARTIAL: real entries in this task's range (logical indices [0, nent))
-};
-static_assert(sizeof(Task) == 32, "Task layout");
 
 struct SolveArgs {
     const Task* tasks;
@@ -104,13 +72,6 @@ struct SqErrArgs {
     int64_t chunk_stride;
 };
 
-// Gram paths: VALU (LDS-staged, fp32 k < 32 and all fp64), MFMA (v_mfma_f32_16x16x4_f32, exact f32
-// products), MFMA_SPLIT (fp32 operands split into narrow terms, fp32 accumulation: fp32-accurate products at a
-// multiple of the f32 MFMA rate): on the fly into three bf16 terms (six v_mfma_f32_16x16x32_bf16 partial products
-// per tile), or -- presplit -- once per half into a scaled two-term fp16 table (three v_mfma_f32_16x16x32_f16).
-// GENERIC: any num_features beyond the wave-per-row kernels (fp32 k > 128, fp64 k > 64): one workgroup per row,
-// the Gram's packed lower triangle in LDS (or a per-workgroup global slab) and a workgroup Cholesky.
-enum class Path : int { VALU = 0, MFMA = 1, MFMA_SPLIT = 2, GENERIC = 3 };
 // Launch geometry of the generic path for (precision, kp): LDS or slab Gram, staged rows per batch, dynamic LDS.
 struct GenericPlan {
     bool g_in_lds;
@@ -139,7 +100,6 @@ hipError_t launch_dual(int kp, int cd, const SolveArgs& a, hipStream_t s);
 // scaled by 2^s, so the 16 values one transposed LDS read hands to a 16-lane group (features (kp/16) j + b,
 // j = 0..15) are 32 contiguous bytes. launch_absmax writes the table's range statistics to amax[0..1] first (zeroed
 // here, on the stream); the presplit kernel and the Gram derive s from it (als_kernels.hip, split_exp).
-__host__ __device__ constexpr int presplit_row_bytes(int kp) { return 4 * kp; }
 hipError_t launch_absmax(const float* src, int64_t n_floats, int kp, uint32_t* amax /* 2 words */, hipStream_t s);
 hipError_t launch_presplit(int kp, const float* src, void* dst, int64_t n_rows, const uint32_t* amax, hipStream_t s);
 // padded column indices -> the per-block order of the presplit gather (n_entries = nnz_padded)

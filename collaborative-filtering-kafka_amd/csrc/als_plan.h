@@ -1,0 +1,116 @@
+// The work plan of a block: its task types (shared with the kernels) and the host arithmetic that turns row degrees
+// into FULL / PARTIAL / REDUCE tasks (als_plan.cpp). Free of HIP and of the environment: the plan is a function of its
+// arguments only, so it builds with any host compiler and is tested on a CPU (tests/test_plan_host.py).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+// Functions the kernels call too; a host compiler sees plain functions.
+#ifdef __HIPCC__
+#define CFK_HOST_DEVICE __host__ __device__
+#else
+#define CFK_HOST_DEVICE
+#endif
+
+namespace cfk {
+
+// One wave-sized unit of work of a half-iteration (host-built once per uploaded block, README.md:146-147:
+// the rating blocks never change, so the work plan is fixed for every iteration).
+//   kind FULL    : gather rows [begin, begin + 4*nsteps) of the padded in-block, accumulate Gram + RHS,
+//                  regularise, Cholesky-solve, store factor row `row`.
+//   kind PARTIAL : same gather/accumulate over one chunk of a long row; store the raw per-lane
+//                  accumulators into partial slot `slot` (no solve).
+//   kind REDUCE  : sum partial slots [slot, slot + nsteps) of row `row` in fixed order, then solve + store.
+enum TaskKind : int32_t { TASK_FULL = 0, TASK_PARTIAL = 1, TASK_REDUCE = 2 };
+
+// Device in-block layout: each row is padded to whole blocks of BLOCK_ENTRIES = 32 entries; padding entries
+// hold col = n_opp_rows (the sentinel zero row kept after the last factor row) and rating 0, so they add
+// nothing and need no masking in the kernels. Entry e of a
+// row is consumed by sub-step t = e / 4 (one MFMA K=4 step) in lane group g = e % 4; inside a block the
+// entries are stored group-major ([g][t], t < 8) so that one lane fetches the column indices of its 8
+// sub-steps with two 16-byte loads.
+constexpr int BLOCK_SUBSTEPS = 8;
+constexpr int BLOCK_ENTRIES = 4 * BLOCK_SUBSTEPS;
+CFK_HOST_DEVICE constexpr int64_t block_position(int64_t e) {
+    const int64_t blk = e / BLOCK_ENTRIES, w = e % BLOCK_ENTRIES;
+    return blk * BLOCK_ENTRIES + (w % 4) * BLOCK_SUBSTEPS + w / 4;
+}
+
+struct alignas(16) Task {
+    int64_t begin;   // entry offset into the padded col/rating arrays (multiple of BLOCK_ENTRIES)
+    int32_t nsteps;  // FULL/PARTIAL: sub-steps holding real entries (ceil(n/4)); the task spans
+                     // ceil(nsteps / BLOCK_SUBSTEPS) blocks. REDUCE: number of partial slots
+    int32_t row;     // local row of the block (factor row = row_offset + row)
+    int32_t slot;    // PARTIAL: slot written; REDUCE: first slot read; FULL: -1
+    int32_t ndeg;    // true in-block size n_j (lambda * n_j * I, MFeatureCalculator.java:92-95)
+    int32_t kind;
+    int32_t nent;    // FULL/PARTIAL: real entries in this task's range (logical indices [0, nent))
+};
+static_assert(sizeof(Task) == 32, "Task layout");
+
+// Gram paths: VALU (LDS-staged, fp32 k < 32 and all fp64), MFMA (v_mfma_f32_16x16x4_f32, exact f32
+// products), MFMA_SPLIT (fp32 operands split into narrow terms, fp32 accumulation: fp32-accurate products at a
+// multiple of the f32 MFMA rate): on the fly into three bf16 terms (six v_mfma_f32_16x16x32_bf16 partial products
+// per tile), or -- presplit -- once per half into a scaled two-term fp16 table (three v_mfma_f32_16x16x32_f16).
+// GENERIC: any num_features beyond the wave-per-row kernels (fp32 k > 128, fp64 k > 64): one workgroup per row,
+// the Gram's packed lower triangle in LDS (or a per-workgroup global slab) and a workgroup Cholesky.
+enum class Path : int { VALU = 0, MFMA = 1, MFMA_SPLIT = 2, GENERIC = 3 };
+
+// Bytes of one row of the pre-split opposite table (als_internal.h, launch_presplit): the fp32 row's size.
+CFK_HOST_DEVICE constexpr int presplit_row_bytes(int kp) { return 4 * kp; }
+
+// Everything the environment can say about the plan (read once per engine by the engine's read_environment, which
+// documents each variable). The defaults are the product's behaviour with nothing set.
+struct PlanKnobs {
+    int interleave = -1;    // ALS_INTERLEAVE: -1 auto, 0 off, 1 wherever the pre-split Gram exists
+    int xcd_ranges = -1;    // ALS_XCD_RANGES: -1 auto, 0 off, 1 on (for interleaved halves)
+    int presplit = -1;      // ALS_PRESPLIT: -1 auto, 0 off, 1 on (where the pre-split Gram exists)
+    bool dual = true;       // ALS_DUAL: short rows in entry space
+    int64_t chunk = 0;      // ALS_CHUNK: >= 1 overrides the contiguous chunk length (rounded up to whole blocks)
+    // debug build only (CFK_DEBUG_KNOBS)
+    int64_t ilv_chunk = 0;  // ALS_ILV_CHUNK: > 0 overrides the interleave length
+    enum TaskOrder { LPT = 0, STAGGER = 1, RANDOM = 2 };
+    int task_order = LPT;   // ALS_TASK_ORDER
+    int64_t stagger_window = 1024;   // ALS_TASK_ORDER=stagger:<W>
+};
+
+struct BlockShape {
+    Path path = Path::VALU;
+    int k = 0, kp = 0;      // features, padded row stride
+    int cu_count = 0;       // compute units of the device
+    int64_t n_opp_rows = 0; // rows of the opposite factor table (its sentinel row not counted)
+};
+
+// How a block's long rows are split and which table its half gathers: decided from the row degrees alone, before the
+// plan is built (the engine fetches the block heads from the device only when `ranges` asks for them).
+struct BlockLayout {
+    int64_t chunk = 0;      // entries per contiguous PARTIAL task of a split row (the generic path never splits)
+    int64_t ilv = 0;        // > 0: rows longer than this are split into interleaved chunks of this many entries
+    bool ranges = false;    // interleaved rows are cut into 8 opposite-slot ranges, one per XCD
+    bool presplit = false;  // the half gathers the pre-split (scaled fp16 h/m) copy of the opposite table
+};
+BlockLayout plan_layout(const PlanKnobs& knobs, const BlockShape& shape, const std::vector<int64_t>& deg);
+
+struct BlockPlan {
+    std::vector<Task> tasks;     // main launch: FULL + PARTIAL in launch order
+    std::vector<Task> reduce;    // one REDUCE per split row, longest first
+    std::vector<Task> dual[3];   // short rows solved in entry space, by padded blocks - 1, longest first
+    std::vector<Task> sq_all;    // every FULL + PARTIAL task incl. the short rows (they cover every entry once)
+    std::vector<int32_t> perm;   // in-block block permutation, dst block i <- src block perm[i]; empty: identity
+    int64_t slots = 0;           // partial slots
+    int64_t ilv_rows = 0, ilv_tasks = 0;   // interleaved rows and their chunk tasks
+    const char* error = nullptr; // set when the block cannot be planned (the vectors are then unspecified)
+};
+// deg[i]: entries of row i; begin[i]: its padded start (begin[n_rows] = padded nnz); bfirst[b]: opposite slot of block
+// b's first entry, read only when layout.ranges.
+BlockPlan plan_build(const PlanKnobs& knobs, const BlockShape& shape, const BlockLayout& layout,
+                     const std::vector<int64_t>& deg, const std::vector<int64_t>& begin,
+                     const std::vector<int32_t>& bfirst);
+
+// Stable partition of a task list by the row chunk of each task's row (chunk c = rows [row_bounds[c],
+// row_bounds[c + 1])): out = the chunks' tasks back to back, chunk c = out[off[c], off[c + 1]). Keeps the
+// longest-first order inside every chunk.
+void partition_by_chunk(const std::vector<Task>& in, int n_chunks, const int64_t* row_bounds, std::vector<Task>& out,
+                        std::vector<int32_t>& off);
+
+}  // namespace cfk

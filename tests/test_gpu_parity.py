@@ -377,8 +377,8 @@ def test_device_block_build_edge_cases(cfk):
 
 
 def _split_slots(deg, nnz_padded):
-    """Partial slots of each split row, as the engine's work plan assigns them (als_engine.cpp chunk_entries /
-    finish_block: rows in order, ceil(deg / chunk) consecutive slots per row longer than chunk)."""
+    """Partial slots of each split row, as the engine's work plan assigns them (als_plan.cpp plan_layout /
+    plan_build: rows in order, ceil(deg / chunk) consecutive slots per row longer than chunk)."""
     c = min(max(nnz_padded // 4096, 1024), 32768)
     c = (c + 31) // 32 * 32
     slots, nxt = {}, 0
