@@ -1,0 +1,175 @@
+"""Degree-ladder blocks, their mutants and the per-row comparator shared by test_rowshapes_host.py (CPU) and
+test_gpu_rowshapes.py (GPU).
+
+The ladder is one purpose-built in-block: a row of every degree 1..330 (the 4-entry step, the 32-entry block, the
+entry-space cut-offs at 32 / 64 / 96 entries and n <= k, and d = chunk, chunk +- 1, m chunk +- 1 under a forced
+64- or 128-entry chunk), twelve rows around 1024, 1056, 2048, 3072 and 4000 entries (split under the unforced
+1024-entry chunk too), and two rows without a rating. The opposite factors are signed with unit-norm rows
+(standard normal / sqrt(k), rounded through fp32): on these the reference's own fp32 error stays near 1e-5 on every
+row, while losing, adding or changing a single entry of a row moves its fp64 solution by ~1e-3 or more. A per-row
+bound of 1e-4 therefore separates a correct kernel from one that drops the last entry of a chunk, miscounts a padded
+block or sums one partial slot too few -- which the global envelope over uniform [0, 1) factors does not
+(test_rowshapes_host.py keeps that contrast on record).
+"""
+from __future__ import annotations
+
+import os
+import sys
+from collections import namedtuple
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import oracle  # noqa: E402  (checker only)
+
+BLOCK_ENTRIES = 32      # als_plan.h: every row is padded to whole blocks of 32 entries
+N_OPP = 4096
+LONG_DEGS = (1023, 1024, 1025, 1055, 1056, 1057, 2047, 2048, 2049, 3071, 3073, 4000)
+# rows 0..329: degree row + 1; one empty row; the twelve long rows; one empty row
+DEFAULT_DEGS = tuple(range(1, 331)) + (0,) + LONG_DEGS + (0,)
+
+BOUND = {"f32": 1e-4, "f64": 1e-8}    # per-row norm-relative error against the fp64 oracle
+MARGIN = 5.0                          # every row's nearest mutant is at least MARGIN * BOUND away
+BUCKETS = ((1, 1), (2, 32), (33, 64), (65, 128), (129, 330), (1023, 1 << 30))
+
+Ladder = namedtuple("Ladder", "blk side coo degs n_opp")
+
+
+def ladder_block(degs=DEFAULT_DEGS, n_opp=N_OPP, seed=0, sort_cols=True) -> Ladder:
+    """One in-block with row i of degs[i] distinct columns drawn from n_opp and ratings 1..5.
+
+    blk: the CSR dict ALSEngine.set_block takes (row_ptr, col, ratings, n_rows); side: the same rows as an oracle.Side;
+    coo: (rows, cols, ratings) for set_block_coo, the entries of all rows shuffled together, each row's entries in
+    their CSR order (the device build's sort is stable). sort_cols: each row's columns ascending by slot, else in the
+    order they were drawn."""
+    rng = np.random.default_rng(seed)
+    degs = np.asarray(degs, np.int64)
+    assert degs.max() <= n_opp
+    row_ptr = np.zeros(len(degs) + 1, np.int64)
+    np.cumsum(degs, out=row_ptr[1:])
+    col = np.zeros(row_ptr[-1], np.int32)
+    for i, d in enumerate(degs):
+        c = rng.choice(n_opp, size=int(d), replace=False)
+        col[row_ptr[i]:row_ptr[i + 1]] = np.sort(c) if sort_cols else c
+    ratings = rng.integers(1, 6, len(col)).astype(np.int16)
+    blk = {"row_ptr": row_ptr, "col": col, "ratings": ratings, "n_rows": len(degs)}
+    side = oracle.Side(np.arange(1, len(degs) + 1, dtype=np.int64), row_ptr.copy(), col.copy(), ratings.copy())
+    arrival = np.repeat(np.arange(len(degs), dtype=np.int32), degs)[rng.permutation(len(col))]
+    pos = np.argsort(arrival, kind="stable")      # arrival positions, grouped by row, ascending inside a row
+    coo_c = np.zeros_like(col)
+    coo_r = np.zeros_like(ratings)
+    coo_c[pos] = col
+    coo_r[pos] = ratings
+    coo = {"n_rows": len(degs), "rows": arrival, "cols": coo_c, "ratings": coo_r}
+    return Ladder(blk, side, coo, degs, n_opp)
+
+
+def factors(n_opp: int, k: int, seed: int = 1) -> np.ndarray:
+    """Signed, zero-mean opposite factors with unit-norm rows (in expectation), exactly representable in fp32."""
+    rng = np.random.default_rng([seed, k])
+    return (rng.standard_normal((n_opp, k)) / np.sqrt(k)).astype(np.float32).astype(np.float64)
+
+
+def _without(side: oracle.Side, which) -> oracle.Side:
+    """Copy of `side` without entry which(d) of every row of d >= 2 entries."""
+    degs = np.diff(side.row_ptr)
+    keep = np.ones(len(side.col), bool)
+    for i, d in enumerate(degs):
+        if d >= 2:
+            keep[side.row_ptr[i] + which(int(d))] = False
+    rp = np.zeros_like(side.row_ptr)
+    np.cumsum(np.where(degs >= 2, degs - 1, degs), out=rp[1:])
+    return oracle.Side(side.ids, rp, side.col[keep].copy(), side.ratings[keep].copy())
+
+
+def mutants(side: oracle.Side) -> dict:
+    """Oracle-side copies of the block that differ from it by one entry in every row of >= 2 entries: what a kernel
+    computes that loses the first, the last or a middle entry of a row, or reads one rating wrong (by the least
+    possible amount, 1)."""
+    out = {"drop_first": _without(side, lambda d: 0), "drop_last": _without(side, lambda d: d - 1),
+           "drop_middle": _without(side, lambda d: d // 2)}
+    rat = side.ratings.copy()
+    degs = np.diff(side.row_ptr)
+    last = side.row_ptr[1:][degs >= 2] - 1
+    rat[last] = np.where(rat[last] < 5, rat[last] + 1, 4)
+    out["last_rating"] = oracle.Side(side.ids, side.row_ptr.copy(), side.col.copy(), rat)
+    return out
+
+
+def references(side: oracle.Side, F: np.ndarray, lam: float):
+    """(fp64 oracle solution, the reference's own fp32 solution) of every row."""
+    return (oracle.update_side(side, F, lam, "f64"),
+            oracle.update_side(side, F.astype(np.float32), lam, "f32"))
+
+
+def row_errors(got, ref64) -> np.ndarray:
+    """Norm-relative error of every row against ref64 (0 where both are exactly zero, inf where only ref64 is)."""
+    got = np.asarray(got, np.float64)
+    ref64 = np.asarray(ref64, np.float64)
+    assert got.shape == ref64.shape, (got.shape, ref64.shape)
+    num = np.linalg.norm(got - ref64, axis=1)
+    den = np.linalg.norm(ref64, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rel = np.where(den > 0, num / den, np.where(num == 0, 0.0, np.inf))
+    return np.where(np.isfinite(got).all(axis=1), rel, np.inf)
+
+
+def rejected_rows(got, ref64, degs, precision) -> np.ndarray:
+    """Per row: True where check_rows would reject it."""
+    degs = np.asarray(degs)
+    rel = row_errors(got, ref64)
+    bad = ~(rel <= BOUND[precision])
+    zero = degs == 0
+    bad[zero] = np.any(np.asarray(got)[zero] != 0, axis=1)
+    return bad
+
+
+def task_kinds(degs, k, chunk, path="mfma_split", dual=True) -> list:
+    """How the plan (als_plan.cpp) solves each row: in entry space, as one FULL task, or split into n PARTIAL slots
+    summed by a REDUCE task. path as ALSEngine.block_path()['gram_path']."""
+    kp = 16 if k <= 16 else 32 if k <= 32 else 64 if k <= 64 else 128
+    max_blocks = {64: 1, 128: 3}.get(kp, 0) if (path == "mfma_split" and dual) else 0
+    chunk = 1 << 62 if path == "generic" else -(-int(chunk) // BLOCK_ENTRIES) * BLOCK_ENTRIES
+    kinds = []
+    for d in np.asarray(degs):
+        d = int(d)
+        if d == 0:
+            kinds.append("empty")
+        elif d > chunk:
+            kinds.append(f"split into {-(-d // chunk)} slots")
+        elif d <= k and -(-d // BLOCK_ENTRIES) <= max_blocks:
+            kinds.append("entry-space")
+        else:
+            kinds.append("FULL")
+    return kinds
+
+
+def check_rows(got, ref64, ref32, degs, precision, kinds=None) -> np.ndarray:
+    """Every row of `got` against the fp64 oracle: norm-relative error <= 1e-4 (fp32) / 1e-8 (fp64) on each row with a
+    rating, rows without one exactly zero; fp32 also p99 <= max(2 x the reference's own fp32 p99, 2e-5). ref32 (the
+    reference's fp32 solution) is read for fp32 only. kinds: per-row task kind for the failure report (task_kinds).
+    Returns the per-row errors; raises AssertionError naming each failing row (the 12 worst), its degree, task kind
+    and error."""
+    degs = np.asarray(degs)
+    assert len(degs) == len(got) == len(ref64)
+    rel = row_errors(got, ref64)
+    bad = rejected_rows(got, ref64, degs, precision)
+    if bad.any():
+        rows = np.nonzero(bad)[0]
+        worst = rows[np.argsort(-np.nan_to_num(rel[rows], posinf=1e300))][:12]
+        lines = [f"row {i} deg {degs[i]} {kinds[i] if kinds is not None else ''}: err {rel[i]:.3e}" for i in worst]
+        raise AssertionError(f"{len(rows)} of {len(degs)} rows beyond {BOUND[precision]:g} ({precision}): "
+                             + "; ".join(lines))
+    rated = degs > 0
+    if precision == "f32":
+        p99 = np.percentile(rel[rated], 99)
+        p99_ref = np.percentile(row_errors(ref32, ref64)[rated], 99)
+        assert p99 <= max(2 * p99_ref, 2e-5), f"p99 {p99:.3e} vs the reference's fp32 p99 {p99_ref:.3e}"
+    return rel
+
+
+def bucket_max(rel, degs) -> dict:
+    """Largest per-row error per degree bucket (BUCKETS), for the record in test_gpu_rowshapes.py's docstring."""
+    degs = np.asarray(degs)
+    return {f"{lo}..{hi}" if hi < 1 << 30 else f">={lo}": float(rel[(degs >= lo) & (degs <= hi)].max())
+            for lo, hi in BUCKETS}

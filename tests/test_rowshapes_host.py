@@ -1,0 +1,130 @@
+"""The power of the degree-ladder check (tests/rowshapes.py), measured with the oracle alone.
+
+For every (k, lambda) that test_gpu_rowshapes.py solves on the GPU: the reference's own fp32 arithmetic passes the
+per-row comparator, the fp64 solution of a block that differs by ONE entry in each row (first / last / middle entry
+dropped, last rating off by 1) is rejected on every row of >= 2 entries, and every such row lies at least 5 bounds
+away from its nearest mutant -- a condition on the inputs (signed unit-norm factors), not a measurement of a kernel.
+The contrast case records why the inputs changed: on uniform [0, 1) factors the global envelope the older tests use
+accepts a row that lost its last entry.
+"""
+import numpy as np
+import pytest
+
+import rowshapes as rs
+
+# (k, lambda) of test_gpu_rowshapes.py
+CASES = [(k, 0.05) for k in (10, 20, 32, 40, 64, 70, 96, 128, 130)] + [(64, 1.0), (128, 1.0)]
+
+
+@pytest.fixture(scope="module")
+def ladder():
+    return rs.ladder_block()
+
+
+def test_ladder_block_is_what_it_says(ladder):
+    blk, side, coo, degs = ladder.blk, ladder.side, ladder.coo, ladder.degs
+    assert np.array_equal(np.diff(blk["row_ptr"]), degs) and blk["n_rows"] == len(degs) == 344
+    assert set(range(1, 331)) | set(rs.LONG_DEGS) | {0} == set(degs.tolist()) and (degs == 0).sum() == 2
+    assert 70_000 < blk["row_ptr"][-1] < 90_000          # the unforced chunk stays 1024 (als_plan.cpp chunk_entries)
+    assert blk["ratings"].min() == 1 and blk["ratings"].max() == 5
+    for sort_cols in (True, False):
+        lad = rs.ladder_block(sort_cols=sort_cols)
+        asc = []
+        for i in range(len(degs)):
+            c = lad.blk["col"][lad.blk["row_ptr"][i]:lad.blk["row_ptr"][i + 1]]
+            assert len(np.unique(c)) == len(c) and (len(c) == 0 or (0 <= c.min() and c.max() < lad.n_opp))
+            asc.append(bool(np.all(np.diff(c) > 0)))
+        assert all(asc) if sort_cols else not all(asc[64:])
+        # the COO arrays are the same rows in another arrival order: a stable sort by row gives the CSR back
+        o = np.argsort(lad.coo["rows"], kind="stable")
+        assert np.array_equal(lad.coo["cols"][o], lad.blk["col"])
+        assert np.array_equal(lad.coo["ratings"][o], lad.blk["ratings"])
+        assert np.array_equal(np.bincount(lad.coo["rows"], minlength=len(degs)), degs)
+        assert not np.array_equal(lad.coo["rows"], np.sort(lad.coo["rows"]))
+    assert np.array_equal(side.row_ptr, blk["row_ptr"]) and np.array_equal(side.col, blk["col"])
+    assert coo["n_rows"] == blk["n_rows"]
+
+
+def test_mutants_differ_by_one_entry_per_row(ladder):
+    degs = ladder.degs
+    m = rs.mutants(ladder.side)
+    assert set(m) == {"drop_first", "drop_last", "drop_middle", "last_rating"}
+    for name in ("drop_first", "drop_last", "drop_middle"):
+        assert np.array_equal(np.diff(m[name].row_ptr), np.where(degs >= 2, degs - 1, degs)), name
+    lr = m["last_rating"]
+    diff = np.nonzero(lr.ratings != ladder.side.ratings)[0]
+    assert np.array_equal(diff, ladder.side.row_ptr[1:][degs >= 2] - 1)
+    assert np.all(np.abs(lr.ratings[diff].astype(int) - ladder.side.ratings[diff]) >= 1)
+    assert lr.ratings.min() >= 1 and lr.ratings.max() <= 5
+
+
+@pytest.mark.parametrize("k,lam", CASES)
+def test_comparator_accepts_the_reference_and_rejects_every_mutant(ladder, k, lam):
+    degs = ladder.degs
+    F = rs.factors(ladder.n_opp, k)
+    ref64, ref32 = rs.references(ladder.side, F, lam)
+    # the reference's own fp32 arithmetic passes, and so does fp64 at the fp64 bar
+    rel32 = rs.check_rows(ref32, ref64, ref32, degs, "f32")
+    rs.check_rows(ref64, ref64, None, degs, "f64")
+    print(f"k={k} lam={lam}: reference fp32 per-row max {rel32.max():.2e}", rs.bucket_max(rel32, degs))
+    two = degs >= 2
+    nearest = np.full(len(degs), np.inf)
+    for name, mside in rs.mutants(ladder.side).items():
+        mut = rs.oracle.update_side(mside, F, lam, "f64")
+        for precision in ("f32", "f64"):
+            bad = rs.rejected_rows(mut, ref64, degs, precision)
+            assert bad[two].all(), (name, precision, np.nonzero(two & ~bad)[0][:8], degs[two & ~bad][:8])
+            assert not bad[~two].any()                 # rows of 0 or 1 entries are the same rows
+            with pytest.raises(AssertionError, match=f"{int(two.sum())} of {len(degs)} rows beyond"):
+                rs.check_rows(mut, ref64, ref32, degs, precision)
+        nearest = np.minimum(nearest, rs.row_errors(mut, ref64))
+    worst = int(np.argmin(np.where(two, nearest, np.inf)))
+    print(f"k={k} lam={lam}: nearest mutant {nearest[worst]:.2e} away (row of {degs[worst]} entries)")
+    assert nearest[worst] >= rs.MARGIN * rs.BOUND["f32"], (k, lam, degs[worst], nearest[worst])
+
+
+def test_comparator_rejects_other_damage(ladder):
+    """Nonzero output on a row without a rating, a NaN, and a wrong shape are failures too; the report names the
+    row, its degree and its task kind."""
+    degs = ladder.degs
+    F = rs.factors(ladder.n_opp, 64)
+    ref64, ref32 = rs.references(ladder.side, F, 0.05)
+    kinds = rs.task_kinds(degs, 64, 64)
+    assert kinds[0] == kinds[31] == "entry-space" and kinds[32] == kinds[63] == "FULL"
+    assert kinds[64] == "split into 2 slots" and kinds[128] == "split into 3 slots" and kinds[330] == "empty"
+    assert kinds[list(degs).index(4000)] == "split into 63 slots"
+    assert rs.task_kinds([96, 97, 70, 71], 70, 1024) == ["FULL", "FULL", "entry-space", "FULL"]       # n <= k only
+    assert rs.task_kinds([96, 97], 128, 1024) == ["entry-space", "FULL"]
+    assert rs.task_kinds([32, 4000], 130, 64, path="generic") == ["FULL", "FULL"]
+    empty = int(np.nonzero(degs == 0)[0][0])
+    got = ref32.copy()
+    got[empty, 3] = 1e-30
+    with pytest.raises(AssertionError, match=f"row {empty} deg 0 empty"):
+        rs.check_rows(got, ref64, ref32, degs, "f32", kinds)
+    got = ref32.copy()
+    got[100, 0] = np.nan
+    with pytest.raises(AssertionError, match="row 100 deg 101 split into 2 slots: err inf"):
+        rs.check_rows(got, ref64, ref32, degs, "f32", kinds)
+    got = ref32.astype(np.float64)
+    got[40] = ref64[40] * (1 + 2e-4)
+    with pytest.raises(AssertionError, match="1 of 344 rows beyond 0.0001 .f32.: row 40 deg 41 FULL: err 2.000e-04"):
+        rs.check_rows(got, ref64, ref32, degs, "f32", kinds)
+    with pytest.raises(AssertionError):
+        rs.check_rows(ref32[:-1], ref64, ref32, degs, "f32", kinds)
+
+
+def test_contrast_old_global_criterion_accepts_a_dropped_entry(ladder):
+    """Uniform [0, 1) factors, k = 128, lambda = 0.05, as the older oracle comparisons draw them: the reference's fp32
+    error on one-rating rows sets the global bound max(3 * rel_ref.max(), 1e-4), and under it the fp64 solution of a
+    row of >= 129 entries that LOST ITS LAST ENTRY passes. The per-row comparator rejects the same row even on these
+    inputs only while the row is short; the ladder's signed factors make every row sensitive."""
+    degs = ladder.degs
+    F = np.random.default_rng(128).random((ladder.n_opp, 128)).astype(np.float32).astype(np.float64)
+    ref64, ref32 = rs.references(ladder.side, F, 0.05)
+    mut = rs.oracle.update_side(rs.mutants(ladder.side)["drop_last"], F, 0.05, "f64")
+    old_bound = max(3 * rs.row_errors(ref32, ref64)[degs > 0].max(), 1e-4)
+    rel = rs.row_errors(mut, ref64)
+    accepted = (degs >= 129) & (rel <= old_bound)
+    print(f"old bound {old_bound:.2e}; dropped-last-entry mutant accepted on {int(accepted.sum())} rows of >= 129 "
+          f"entries, e.g. degree {degs[accepted][:5]}, error {rel[accepted][:5]}")
+    assert accepted.any(), (old_bound, rel[degs >= 129].min())
