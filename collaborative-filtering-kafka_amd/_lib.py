@@ -84,6 +84,8 @@ SIGNATURES = [
     ("als_comm_wait", _i, [_vp]),
     ("als_comm_set_timeout", _i, [_vp, _i64]),
     ("als_predict", _i, [_vp, _pi64, _i64, _pi64, _i64, _pf]),
+    ("als_recommend", _i, [_vp, _pi64, _i64, _pi64, _i64, _i, _pi64, _pi32, _pi32, _pf]),
+    ("als_recommend_plan", _i, [_vp, _i64, _i64, _i, _pi64]),
     ("als_sq_error", _i, [_vp, _i, _pd, _pi64]),
     ("als_synchronize", _i, [_vp]),
     ("als_integrity_status", _i, [_vp, ctypes.POINTER(ctypes.c_uint32), _i]),
@@ -115,6 +117,7 @@ SIGNATURES = [
     ("als_u01", _f, [_u64, _i64, ctypes.c_int32]),
     ("als_write_prediction_csv", _i, [ctypes.c_char_p, _pf, _i64, _i64, _pf, _i64, _i64, _i]),
     ("als_write_prediction_matrix_csv", _i, [ctypes.c_char_p, _pf, _i64, _i64]),
+    ("als_write_recommendations_csv", _i, [ctypes.c_char_p, _pi64, _i64, _i, _pi64, _pf]),
     ("als_feature_message_size", _i64, [_i64, _i]),
     ("als_feature_message_encode", _i, [ctypes.c_int32, _pi32, _i64, _pf, _i, _pu8, _i64, _pi64]),
     ("als_feature_message_decode", _i, [_pu8, _i64, _i, _pi32, _pi32, _i64, _pi64, _pf]),

@@ -32,6 +32,40 @@ def _table_digest(t: torch.Tensor) -> int:
     return int((w * ((2 * i + 1) * 0x9E3779B1)).sum().item())
 
 
+def shard_user_rows(ds: Dataset, world: int, rank: int) -> np.ndarray:
+    """Factor rows (slots) of rank `rank`'s users in local-row order (ascending raw id), under the chunk-major slot
+    layout: local row i -> row_offset + (i // Sc) G Sc + i % Sc (include/als_host.h "Slot layout")."""
+    info = ds.shard_info(SIDE_USER, world, rank)
+    i = np.arange(info["n_rows"], dtype=np.int64)
+    sc, nc = ds.slot_layout(SIDE_USER, world)
+    return (info["row_offset"] + ((i // sc) * (world * sc) + i % sc if nc > 1 else i)).astype(np.int64)
+
+
+def seen_exclusions(ds: Dataset, world: int, rank: int, movie_rows) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """What ALSEngine.recommend needs to leave out the movies a user has already rated. For rank `rank`'s users in
+    local-row order (ascending raw id): (user_factor_rows, excl_ptr, excl_idx), excl_idx[excl_ptr[i]:excl_ptr[i + 1]]
+    = the positions in `movie_rows` (movie factor rows = slots, any subset, repeats allowed) of user i's rated movies,
+    ascending; rated movies outside the candidate set are dropped. Pure host code; the factor rows honour the
+    chunk-major slot layout (shard_user_rows)."""
+    blk = ds.shard_block(SIDE_USER, world, rank)
+    n = blk["n_rows"]
+    i = np.arange(n, dtype=np.int64)
+    rows = shard_user_rows(ds, world, rank)
+    mr = np.ascontiguousarray(movie_rows, np.int64)
+    order = np.argsort(mr, kind="stable")              # positions grouped by slot: the inverse of movie_rows
+    by_slot = mr[order]
+    col = blk["col"].astype(np.int64)
+    lo = np.searchsorted(by_slot, col, "left")
+    cnt = np.searchsorted(by_slot, col, "right") - lo    # 0: not a candidate; > 1: the slot is listed several times
+    user = np.repeat(np.repeat(i, np.diff(blk["row_ptr"])), cnt)
+    start = np.cumsum(cnt) - cnt
+    pos = order[np.repeat(lo, cnt) + (np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(start, cnt))]
+    keep = np.lexsort((pos, user))                       # ascending position inside every user
+    excl_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(user, minlength=n), out=excl_ptr[1:])
+    return rows, excl_ptr, pos[keep].astype(np.int32)
+
+
 class ALSApp:
     # a movie factor table above this is exchanged in chunks (N > 1): configs[4]'s 256 MB item table (all-gather ~1.7 ms
     # at G = 8), not the 9 MB k = 128 Netflix one -- its 4 chunk launches cost more in launch tails than the overlap of a
@@ -242,6 +276,25 @@ class ALSApp:
         """FeatureCollector.calculatePredictionMatrix (FeatureCollector.java:90-101): users x movies, both in
         ascending id order, computed on the GPU from the (gathered) factor replicas."""
         return self.engine.predict(self.ds.slots(SIDE_USER, self.world), self.ds.slots(SIDE_MOVIE, self.world))
+
+    def recommend(self, top_n: int, exclude_seen: bool = True) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Top-N movies of every user of this rank's shard against all movies, from the (gathered) factor replicas:
+        (user_ids [n], movie_ids [n, top_n], scores [n, top_n]) in raw ids, users ascending, best first. Candidates are
+        taken in ascending movie id, so equal scores go to the smaller movie id; movie id -1 / score -inf where a user
+        has fewer than top_n eligible movies. exclude_seen leaves out the movies the user has rated. No collective:
+        every rank answers for its own users."""
+        movie_ids = self.ds.ids(SIDE_MOVIE)
+        movie_rows = self.ds.slots(SIDE_MOVIE, self.world)       # ascending id -> factor row
+        if exclude_seen:
+            user_rows, excl_ptr, excl_idx = seen_exclusions(self.ds, self.world, self.rank, movie_rows)
+            idx, score = self.engine.recommend(user_rows, movie_rows, top_n, (excl_ptr, excl_idx))
+        else:
+            idx, score = self.engine.recommend(shard_user_rows(self.ds, self.world, self.rank), movie_rows, top_n)
+        user_ids = self.ds.ids(SIDE_USER)
+        if self.world > 1:
+            user_ids = user_ids[user_ids % self.world == self.rank]
+        out = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
+        return user_ids, out.astype(np.int64), score
 
     def sq_error(self):
         """Sum of squared errors over all observed ratings (all ranks) and the rating count."""

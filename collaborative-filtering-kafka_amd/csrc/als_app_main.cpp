@@ -1,7 +1,7 @@
 // als_app -- command-line replacement for ALSAppRunner (apps/ALSAppRunner.java:10-37) on 1..G MI355X.
 //
 //   als_app NUM_PARTITIONS NUM_FEATURES LAMBDA NUM_ITERATIONS dataset NUM_MOVIES NUM_USERS
-//           [--precision f32|f64] [--seed S] [--gpus G] [--out DIR]
+//           [--precision f32|f64] [--seed S] [--gpus G] [--out DIR] [--top-n N] [--no-matrix]
 //
 // Same 7 positional arguments (README.md:35); the extras are optional trailing flags. The run follows the
 // reference topology (ALSApp.java:52-184) bulk-synchronously: ingest (NetflixDataFormatProducer), in-blocks
@@ -12,6 +12,9 @@
 // (or --gpus), so that shard(id) = id % G = (id % NUM_PARTITIONS) % G (PureModStreamPartitioner.java:9-10).
 // One process drives the G engines (one per GPU); every half ends with an RCCL all-gather of each shard
 // (als_allgather_shard), the replacement for the per-iteration feature topics (ALSApp.java:105-151).
+// --top-n N (1..64) additionally writes <out>/recommendations_<timestamp>: per user, ascending id, its N best-scoring
+// movies not rated yet as lines "userId,movieId,score" (als_recommend: no dense matrix); --no-matrix skips the
+// prediction matrix and its CSV, which do not fit at full scale. Without them the output is the reference's.
 // Deviations that turn reference hangs into errors: duplicate (user, movie) pairs, and NUM_MOVIES /
 // NUM_USERS not equal to the rated-entity counts (FeatureCollector.java:43 would never fire).
 #include <sys/stat.h>
@@ -88,6 +91,8 @@ int main(int argc, char** argv) {
     unsigned long long seed = 42;
     int gpus = 0;
     std::string outdir = "./predictions";
+    long long top_n = 0;
+    bool matrix = true;
     for (int i = 8; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--precision" && i + 1 < argc) {
@@ -101,6 +106,13 @@ int main(int argc, char** argv) {
             gpus = atoi(argv[++i]);
         } else if (a == "--out" && i + 1 < argc) {
             outdir = argv[++i];
+        } else if (a == "--top-n" && i + 1 < argc) {
+            if (!parse_int(argv[++i], 1, 64, top_n)) {
+                fprintf(stderr, "als_app: --top-n 1..64\n");
+                return 1;
+            }
+        } else if (a == "--no-matrix") {
+            matrix = false;
         } else {
             fprintf(stderr, "als_app: unknown option %s\n", a.c_str());
             return 1;
@@ -198,20 +210,48 @@ int main(int argc, char** argv) {
     printf("ALS: %lld iterations in %.3f s (%.3e ratings/s per iteration); MSE %.6f RMSE %.6f\n", N, secs,
            N > 0 ? (double)nnz * N / secs : 0.0, cnt ? se / cnt : 0.0, cnt ? std::sqrt(se / cnt) : 0.0);
 
-    // FeatureCollector: factors in ascending id order (their slots in engine 0's gathered replicas); U M^T on the
-    // GPU with the collector's Java-float dot, then the EJML CSV text on the host.
-    printf("Start Prediction Matrix Computation at %s\n", java_timestamp().c_str());
     std::vector<int64_t> urows(nu), mrows(nm);
     if (als_dataset_slots(ds, ALS_SIDE_USER, G, urows.data()) != ALS_OK ||
         als_dataset_slots(ds, ALS_SIDE_MOVIE, G, mrows.data()) != ALS_OK)
         return die("slots");
-    std::vector<float> pred((size_t)nu * (size_t)nm);
-    if (als_predict(eng[0], urows.data(), nu, mrows.data(), nm, pred.data()) != ALS_OK) return die("predict");
-    mkdir(outdir.c_str(), 0755);
-    const std::string path = outdir + "/prediction_matrix_" + java_timestamp();
-    printf("Done at %s\n", java_timestamp().c_str());
-    if (als_write_prediction_matrix_csv(path.c_str(), pred.data(), nu, nm) != ALS_OK) return die("csv");
-    printf("Prediction matrix: %s\n", path.c_str());
+    if (matrix || top_n > 0) mkdir(outdir.c_str(), 0755);
+    if (matrix) {
+        // FeatureCollector: factors in ascending id order (their slots in engine 0's gathered replicas); U M^T on the
+        // GPU with the collector's Java-float dot, then the EJML CSV text on the host.
+        printf("Start Prediction Matrix Computation at %s\n", java_timestamp().c_str());
+        std::vector<float> pred((size_t)nu * (size_t)nm);
+        if (als_predict(eng[0], urows.data(), nu, mrows.data(), nm, pred.data()) != ALS_OK) return die("predict");
+        const std::string path = outdir + "/prediction_matrix_" + java_timestamp();
+        printf("Done at %s\n", java_timestamp().c_str());
+        if (als_write_prediction_matrix_csv(path.c_str(), pred.data(), nu, nm) != ALS_OK) return die("csv");
+        printf("Prediction matrix: %s\n", path.c_str());
+    }
+    if (top_n > 0) {
+        // Candidates = all movies in ascending id (ties go to the smaller id); excluded per user = the movies it rated:
+        // the unsharded user in-block lists them as dense movie indices, which are the candidate positions.
+        int64_t n_rows, row_off, bnnz, s1, ns1;
+        if (als_dataset_shard_info(ds, ALS_SIDE_USER, 1, 0, &n_rows, &row_off, &bnnz, &s1, &ns1) != ALS_OK)
+            return die("shard_info");
+        std::vector<int64_t> eptr(n_rows + 1), uid(nu), mid(nm);
+        std::vector<int32_t> eidx(bnnz);
+        std::vector<int16_t> erat(bnnz);
+        if (als_dataset_shard_block(ds, ALS_SIDE_USER, 1, 0, eptr.data(), eidx.data(), erat.data(), nullptr) != ALS_OK)
+            return die("user in-blocks");
+        for (int64_t u = 0; u < n_rows; ++u) std::sort(eidx.begin() + eptr[u], eidx.begin() + eptr[u + 1]);
+        if (als_dataset_ids(ds, ALS_SIDE_USER, uid.data()) != ALS_OK || als_dataset_ids(ds, ALS_SIDE_MOVIE, mid.data()) != ALS_OK)
+            return die("ids");
+        std::vector<int32_t> idx((size_t)nu * top_n);
+        std::vector<float> score((size_t)nu * top_n);
+        if (als_recommend(eng[0], urows.data(), nu, mrows.data(), nm, (int)top_n, eptr.data(), eidx.data(), idx.data(),
+                          score.data()) != ALS_OK)
+            return die("recommend");
+        std::vector<int64_t> movie((size_t)nu * top_n);
+        for (size_t i = 0; i < idx.size(); ++i) movie[i] = idx[i] >= 0 ? mid[idx[i]] : -1;
+        const std::string path = outdir + "/recommendations_" + java_timestamp();
+        if (als_write_recommendations_csv(path.c_str(), uid.data(), nu, (int)top_n, movie.data(), score.data()) != ALS_OK)
+            return die("recommendations");
+        printf("Recommendations: %s\n", path.c_str());
+    }
     for (auto* e : eng) als_engine_destroy(e);
     als_dataset_destroy(ds);
     return 0;

@@ -833,4 +833,32 @@ int als_write_prediction_matrix_csv(const char* path, const float* P, int64_t n_
     return write_csv(path, n_users, n_movies, [&](int64_t i, int64_t j) { return P[i * n_movies + j]; });
 }
 
+int als_write_recommendations_csv(const char* path, const int64_t* user_ids, int64_t n_users, int top_n,
+                                  const int64_t* movie_ids, const float* scores) {
+    if (!path || n_users < 0 || top_n < 1 || (n_users > 0 && (!user_ids || !movie_ids || !scores)))
+        return report(fail(ALS_ERR_INVALID_ARGUMENT, "bad arguments"));
+    FILE* f = fopen(path, "wb");
+    if (!f) return report(fail(ALS_ERR_IO, "cannot create %s", path));
+    std::string line;
+    for (int64_t i = 0; i < n_users; ++i) {
+        line.clear();
+        for (int j = 0; j < top_n; ++j) {
+            const int64_t m = movie_ids[i * top_n + j];
+            if (m < 0) continue;
+            line += std::to_string((long long)user_ids[i]);
+            line.push_back(',');
+            line += std::to_string((long long)m);
+            line.push_back(',');
+            line += java_double((double)scores[i * top_n + j]);
+            line.push_back('\n');
+        }
+        if (fwrite(line.data(), 1, line.size(), f) != line.size()) {
+            fclose(f);
+            return report(fail(ALS_ERR_IO, "write failed: %s", path));
+        }
+    }
+    if (fclose(f) != 0) return report(fail(ALS_ERR_IO, "close failed: %s", path));
+    return ALS_OK;
+}
+
 }  // extern "C"

@@ -131,6 +131,8 @@ struct als_engine {
     void* d_split = nullptr;        // pre-split opposite table (cfk::launch_presplit), sized for the larger need
     size_t split_bytes = 0;
     uint32_t* d_amax = nullptr;     // bits of the pre-split table's largest |x| (cfk::launch_absmax): its scale
+    void* d_rec = nullptr;          // als_recommend's own grow-only workspace (rows, exclusion CSR, partial and final
+    size_t rec_bytes = 0;           //   lists): never d_partials / d_split / d_amax, which a half in progress owns
     void* h_stage = nullptr;        // pinned staging of als_write_factors / als_read_factors (copy kernels)
     size_t stage_bytes = 0;
     uint32_t* d_integrity = nullptr;   // cfk::INTEGRITY_WORDS: partial slots that failed their check
@@ -397,6 +399,7 @@ int als_engine_destroy(als_engine* e) {
         if (f.owned) (void)hipFree(f.ptr);
     (void)hipFree(e->d_partials);
     (void)hipFree(e->d_split);
+    (void)hipFree(e->d_rec);
     (void)hipHostFree(e->h_stage);
     (void)hipFree(e->d_integrity);
     (void)hipFree(e->d_amax);
@@ -1023,6 +1026,109 @@ int als_predict(als_engine* e, const int64_t* user_rows, int64_t n_users, const 
     if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
     cleanup();
     if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_predict: %s", hipGetErrorString(st));
+    return sync_checked(e);
+}
+
+int als_recommend_plan(const als_engine* e, int64_t n_users, int64_t n_movies, int top_n, int64_t info[4]) {
+    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (n_users < 0 || n_movies < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "negative counts");
+    if (top_n < 1 || top_n > cfk::REC_MAX_TOP_N)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "top_n must be 1..%d, got %d", cfk::REC_MAX_TOP_N, top_n);
+    const cfk::RecommendPlan p = cfk::recommend_plan(n_users, n_movies, top_n, e->kp, e->cu_count);
+    info[0] = p.user_tile;
+    info[1] = p.segments;
+    info[2] = p.seg_len;
+    info[3] = p.lds_bytes;
+    return ALS_OK;
+}
+
+int als_recommend(als_engine* e, const int64_t* user_rows, int64_t n_users, const int64_t* movie_rows, int64_t n_movies,
+                  int top_n, const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* host_idx, float* host_score) {
+    if (int r = check_engine(e)) return r;
+    if (n_users < 0 || n_movies < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "negative counts");
+    if (top_n < 1 || top_n > cfk::REC_MAX_TOP_N)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: top_n must be 1..%d, got %d", cfk::REC_MAX_TOP_N, top_n);
+    if ((excl_ptr == nullptr) != (excl_idx == nullptr))
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: excl_ptr and excl_idx must both be given or both be NULL");
+    if (n_movies > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: n_movies must be below 2^31");
+    const Factors& U = e->fac[ALS_SIDE_USER];
+    const Factors& M = e->fac[ALS_SIDE_MOVIE];
+    if (!U.ptr || !M.ptr) return fail(ALS_ERR_STATE, "als_recommend: factor matrices not allocated/bound");
+    if (n_users == 0 || n_movies == 0) return ALS_OK;
+    if (!user_rows || !movie_rows || !host_idx || !host_score) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    for (int64_t i = 0; i < n_users; ++i)
+        if (user_rows[i] < 0 || user_rows[i] >= U.n_rows) return fail(ALS_ERR_INVALID_ARGUMENT, "user row out of range");
+    for (int64_t i = 0; i < n_movies; ++i)
+        if (movie_rows[i] < 0 || movie_rows[i] >= M.n_rows) return fail(ALS_ERR_INVALID_ARGUMENT, "movie row out of range");
+    int64_t ex0 = 0, ex_nnz = 0;
+    if (excl_ptr) {   // O(nnz): ranges in order, positions strictly ascending per user and inside the candidate set
+        ex0 = excl_ptr[0];
+        if (ex0 < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: excl_ptr[0] is negative");
+        for (int64_t u = 0; u < n_users; ++u) {
+            const int64_t lo = excl_ptr[u], hi = excl_ptr[u + 1];
+            if (hi < lo) return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: excl_ptr decreases at user %lld", (long long)u);
+            for (int64_t x = lo; x < hi; ++x) {
+                if (excl_idx[x] < 0 || excl_idx[x] >= n_movies)
+                    return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: excluded position %d of user %lld is outside [0, %lld)",
+                                (int)excl_idx[x], (long long)u, (long long)n_movies);
+                if (x > lo && excl_idx[x] <= excl_idx[x - 1])
+                    return fail(ALS_ERR_INVALID_ARGUMENT,
+                                "als_recommend: excluded positions of user %lld are not strictly ascending", (long long)u);
+            }
+        }
+        ex_nnz = excl_ptr[n_users] - ex0;
+    }
+    const cfk::RecommendPlan p = cfk::recommend_plan(n_users, n_movies, top_n, e->kp, e->cu_count);
+    if (p.lds_bytes > cfk::REC_LDS_LIMIT) return fail(ALS_ERR_UNSUPPORTED, "als_recommend: launch plan exceeds the LDS");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int r = wait_gathers(e, true, true)) return r;
+    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t off_eptr = p.workspace_bytes;
+    const int64_t off_eidx = off_eptr + (excl_ptr ? align((n_users + 1) * 8) : 0);
+    const size_t need = (size_t)(off_eidx + (excl_ptr ? align(ex_nnz * 4) : 0));
+    if (need > e->rec_bytes) {   // grow-only; the stream may still be reading the old one
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        (void)hipFree(e->d_rec);
+        e->d_rec = nullptr;
+        e->rec_bytes = 0;
+        const hipError_t st = hipMalloc(&e->d_rec, need);
+        if (st != hipSuccess)
+            return fail(ALS_ERR_OUT_OF_MEMORY, "als_recommend: hipMalloc(%zu): %s", need, hipGetErrorString(st));
+        e->rec_bytes = need;
+    }
+    char* w = (char*)e->d_rec;
+    int64_t* d_u = (int64_t*)(w + p.off_urows);
+    int64_t* d_m = (int64_t*)(w + p.off_mrows);
+    int32_t* d_idx = (int32_t*)(w + p.off_idx);
+    float* d_score = (float*)(w + p.off_score);
+    float* d_ps = (float*)(w + p.off_part_score);
+    int32_t* d_pp = (int32_t*)(w + p.off_part_pos);
+    int64_t* d_eptr = excl_ptr ? (int64_t*)(w + off_eptr) : nullptr;
+    int32_t* d_eidx = excl_ptr ? (int32_t*)(w + off_eidx) : nullptr;
+    std::vector<int64_t> eptr0;   // the device ranges index the uploaded slice: rebased to 0
+    hipError_t st = hipMemcpyAsync(d_u, user_rows, n_users * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_m, movie_rows, n_movies * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && excl_ptr) {
+        const int64_t* src = excl_ptr;
+        if (ex0 != 0) {
+            eptr0.resize(n_users + 1);
+            for (int64_t u = 0; u <= n_users; ++u) eptr0[u] = excl_ptr[u] - ex0;
+            src = eptr0.data();
+        }
+        st = hipMemcpyAsync(d_eptr, src, (n_users + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+        if (st == hipSuccess && ex_nnz > 0)
+            st = hipMemcpyAsync(d_eidx, excl_idx + ex0, ex_nnz * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    }
+    if (st == hipSuccess)
+        st = cfk::launch_recommend(e->precision, U.ptr, M.ptr, e->kp, e->k, d_u, n_users, d_m, n_movies, top_n, p, d_eptr,
+                                   d_eidx, d_ps, d_pp, d_score, d_idx, e->stream);
+    const size_t ob = (size_t)n_users * (size_t)top_n * 4;
+    if (st == hipSuccess) st = hipMemcpyAsync(host_idx, d_idx, ob, hipMemcpyDeviceToHost, e->stream);
+    if (st == hipSuccess) st = hipMemcpyAsync(host_score, d_score, ob, hipMemcpyDeviceToHost, e->stream);
+    // the host arrays (eptr0 too) are pageable: the stream has to pass the copies before this call returns
+    const hipError_t st2 = hipStreamSynchronize(e->stream);
+    if (st == hipSuccess) st = st2;
+    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_recommend: %s", hipGetErrorString(st));
     return sync_checked(e);
 }
 

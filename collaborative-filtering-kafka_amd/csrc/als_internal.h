@@ -113,6 +113,14 @@ hipError_t launch_download(const void* src, void* host_pinned, size_t bytes, hip
 // out[u][m] = Java-float dot of U row urows[u] and M row mrows[m] (device arrays; out row-major n_u x n_m).
 hipError_t launch_predict(int precision, const void* U, const void* M, int kp, int k, const int64_t* urows,
                           int64_t n_u, const int64_t* mrows, int64_t n_m, float* out, hipStream_t s);
+// Top-N of the same dots per query user (als_recommend.hip): the scoring kernel sweeps plan.segments candidate
+// segments per user tile; one segment writes out_pos / out_score [n_u][top_n] itself, several write the partial lists
+// (part_*, [n_u * segments][top_n]) that the merge kernel reduces. excl_ptr / excl_idx: device CSR of excluded
+// candidate positions per query user (ascending), or both NULL.
+hipError_t launch_recommend(int precision, const void* U, const void* M, int kp, int k, const int64_t* urows,
+                            int64_t n_users, const int64_t* mrows, int64_t n_cand, int top_n,
+                            const RecommendPlan& plan, const int64_t* excl_ptr, const int32_t* excl_idx,
+                            float* part_score, int32_t* part_pos, float* out_score, int32_t* out_pos, hipStream_t s);
 hipError_t launch_sq_error(int precision, int kp, const SqErrArgs& a, hipStream_t s);
 // Per-lane accumulator words (elements of the engine precision) of one partial slot: nacc * 64.
 int partial_words_per_lane(int precision, int kp, Path path);

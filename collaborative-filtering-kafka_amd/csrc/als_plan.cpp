@@ -342,4 +342,35 @@ void partition_by_chunk(const std::vector<Task>& in, int n_chunks, const int64_t
     }
 }
 
+RecommendPlan recommend_plan(int64_t n_users, int64_t n_cand, int top_n, int kp, int cu_count) {
+    (void)kp;
+    RecommendPlan p;
+    n_users = std::max<int64_t>(n_users, 0);
+    n_cand = std::max<int64_t>(n_cand, 0);
+    top_n = std::min(std::max(top_n, 1), REC_MAX_TOP_N);
+    const int64_t cus = std::max(1, cu_count);
+    p.user_tiles = (n_users + REC_USER_TILE - 1) / REC_USER_TILE;
+    const int64_t cand_tiles = std::max<int64_t>(1, (n_cand + REC_CAND_TILE - 1) / REC_CAND_TILE);
+    int64_t S = 1;
+    if (p.user_tiles < cus) {
+        const int64_t ut = std::max<int64_t>(1, p.user_tiles);
+        S = std::min({cand_tiles, (4 * cus + ut - 1) / ut, REC_MAX_SEGMENTS});
+    }
+    const int64_t seg_tiles = (cand_tiles + S - 1) / S;
+    p.segments = (cand_tiles + seg_tiles - 1) / seg_tiles;   // no empty segment
+    p.seg_len = seg_tiles * REC_CAND_TILE;
+    p.lds_bytes = recommend_lds_bytes(top_n);
+    p.partial_rows = p.segments > 1 ? n_users * p.segments : 0;
+    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
+    int64_t off = 0;
+    p.off_urows = off, off += align(n_users * 8);
+    p.off_mrows = off, off += align(n_cand * 8);
+    p.off_idx = off, off += align(n_users * top_n * 4);
+    p.off_score = off, off += align(n_users * top_n * 4);
+    p.off_part_score = off, off += align(p.partial_rows * top_n * 4);
+    p.off_part_pos = off, off += align(p.partial_rows * top_n * 4);
+    p.workspace_bytes = off;
+    return p;
+}
+
 }  // namespace cfk

@@ -113,4 +113,42 @@ BlockPlan plan_build(const PlanKnobs& knobs, const BlockShape& shape, const Bloc
 void partition_by_chunk(const std::vector<Task>& in, int n_chunks, const int64_t* row_bounds, std::vector<Task>& out,
                         std::vector<int32_t>& off);
 
+// ---- top-N recommendation (als_recommend.hip) ----------------------------------------------------------------------
+// A 256-thread workgroup owns REC_USER_TILE query users and sweeps the REC_CAND_TILE-candidate tiles of one candidate
+// segment, REC_FEAT_CHUNK features staged per pass (row pitch REC_PITCH floats: odd, so the 16 rows a wave reads in
+// one step fall into 16 banks). Per user: a sorted best-N list, a threshold and a queue of REC_QUEUE survivors.
+constexpr int REC_USER_TILE = 64;
+constexpr int REC_CAND_TILE = 64;
+constexpr int REC_FEAT_CHUNK = 32;
+constexpr int REC_PITCH = REC_FEAT_CHUNK + 1;
+constexpr int REC_QUEUE = 32;
+constexpr int REC_MAX_TOP_N = 64;
+constexpr int64_t REC_MAX_SEGMENTS = 65535;   // gridDim.y
+constexpr int64_t REC_LDS_LIMIT = 160 * 1024; // LDS of one gfx950 compute unit
+// Dynamic LDS of the scoring kernel in 4-byte words: the two staged tiles, the queues (score, position), the lists
+// (score, position), then per user threshold score, threshold position, queue count, list count, and the overflow flag.
+CFK_HOST_DEVICE constexpr int64_t recommend_lds_bytes(int top_n) {
+    return 4 * ((int64_t)(REC_USER_TILE + REC_CAND_TILE) * REC_PITCH + 2 * (int64_t)REC_USER_TILE * REC_QUEUE +
+                2 * (int64_t)REC_USER_TILE * top_n + 4 * (int64_t)REC_USER_TILE + 4);
+}
+
+struct RecommendPlan {
+    int user_tile = REC_USER_TILE, cand_tile = REC_CAND_TILE;
+    int64_t user_tiles = 0;     // workgroups along the users (gridDim.x)
+    int64_t segments = 1;       // S: candidate segments (gridDim.y); > 1: partial lists + the merge kernel
+    int64_t seg_len = 0;        // candidates per segment: whole candidate tiles, the last segment may be short
+    int64_t lds_bytes = 0;      // dynamic LDS of one workgroup
+    int64_t partial_rows = 0;   // S > 1: (user, segment) partial lists of top_n (score, position) pairs; else 0
+    // byte offsets into the call's workspace (256-byte aligned): user rows, candidate rows (int64), final positions
+    // (int32) and scores (float) [n_users][top_n], partial scores and positions [partial_rows][top_n]
+    int64_t off_urows = 0, off_mrows = 0, off_idx = 0, off_score = 0, off_part_score = 0, off_part_pos = 0;
+    int64_t workspace_bytes = 0;   // all of the above (the exclusion CSR comes on top: it depends on the caller's
+                                   // data, not on the shape)
+};
+// Pure function of its arguments. S = 1 when the user tiles alone give every compute unit a workgroup; otherwise the
+// candidates are cut so that user tiles x S reaches 4 workgroups per compute unit (the scoring kernel's occupancy at
+// top_n <= 16), at least one candidate tile per segment. kp does not enter today (features are staged in chunks of
+// REC_FEAT_CHUNK whatever the row length); it is part of the signature so that a kp-dependent tile can come later.
+RecommendPlan recommend_plan(int64_t n_users, int64_t n_cand, int top_n, int kp, int cu_count);
+
 }  // namespace cfk

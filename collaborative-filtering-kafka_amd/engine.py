@@ -408,6 +408,37 @@ class ALSEngine:
              ptr(out, ctypes.c_float))
         return out
 
+    def recommend(self, user_rows, movie_rows, top_n: int, exclude=None) -> tuple[np.ndarray, np.ndarray]:
+        """Per query user the top_n best-scoring candidates (als_recommend): (idx int32 [n, top_n] = positions in
+        movie_rows, score float32 [n, top_n]), best first, ties toward the smaller position, padded with -1 / -inf.
+        The scores are predict()'s cells bit for bit; the dense matrix is never formed. exclude: (excl_ptr, excl_idx),
+        a CSR of candidate positions (ascending per user) that must not be returned."""
+        ur = np.ascontiguousarray(user_rows, np.int64)
+        mr = np.ascontiguousarray(movie_rows, np.int64)
+        n = int(top_n)
+        idx = np.full((len(ur), max(n, 0)), -1, np.int32)
+        score = np.full((len(ur), max(n, 0)), -np.inf, np.float32)
+        ep = ei = None
+        if exclude is not None:
+            ep = np.ascontiguousarray(exclude[0], np.int64)
+            ei = np.ascontiguousarray(exclude[1], np.int32)
+            if len(ep) != len(ur) + 1:
+                raise ValueError("exclude: excl_ptr must have len(user_rows) + 1 entries")
+            if len(ep) and int(ep[-1]) > len(ei):
+                raise ValueError("exclude: excl_ptr points past excl_idx")
+            if ei.size == 0:
+                ei = np.zeros(1, np.int32)   # a valid pointer for an empty list
+        call("als_recommend", self._h, ptr(ur, ctypes.c_int64), len(ur), ptr(mr, ctypes.c_int64), len(mr), n,
+             ptr(ep, ctypes.c_int64) if ep is not None else None, ptr(ei, ctypes.c_int32) if ei is not None else None,
+             ptr(idx, ctypes.c_int32), ptr(score, ctypes.c_float))
+        return idx, score
+
+    def recommend_plan(self, n_users: int, n_movies: int, top_n: int) -> dict:
+        """Launch shape recommend() would choose (als_recommend_plan)."""
+        v = (ctypes.c_int64 * 4)()
+        call("als_recommend_plan", self._h, int(n_users), int(n_movies), int(top_n), v)
+        return {"user_tile": v[0], "segments": v[1], "segment_len": v[2], "lds_bytes": v[3]}
+
     def sq_error(self, side="movie"):
         se = ctypes.c_double()
         cnt = ctypes.c_int64()

@@ -174,6 +174,28 @@ int als_comm_set_timeout(als_engine* e, int64_t timeout_ms);
 int als_predict(als_engine* e, const int64_t* user_rows, int64_t n_users, const int64_t* movie_rows,
                 int64_t n_movies, float* host_out);
 
+/* Top-N recommendation from the resident factors (no reference counterpart: the reference can only write the dense
+ * matrix): per query user the top_n best-scoring candidates that are not excluded. Scoring and selection are fused on
+ * the GPU; the users x movies matrix is never materialised, and n_users is not limited as in als_predict.
+ *  - user_rows / movie_rows: factor rows (slots) of U / M, any order, repeats allowed; n_movies < 2^31.
+ *  - Score of (u, c) = exactly als_predict's cell for (user_rows[u], movie_rows[c]), bit for bit.
+ *  - Order (total): higher score first, compared as floats (-0.0 == +0.0); equal scores by the smaller candidate
+ *    position c (the index into movie_rows). The result is deterministic.
+ *  - host_idx[u * top_n + j] = candidate position of the j-th best, host_score its score; a user with fewer than top_n
+ *    eligible candidates gets idx -1 / score -INFINITY in the remaining entries. top_n: 1..64.
+ *  - excl_idx[excl_ptr[u] .. excl_ptr[u + 1]) = candidate positions excluded for query user u: strictly ascending per
+ *    user, in [0, n_movies) (checked on the host, ALS_ERR_INVALID_ARGUMENT). Both NULL: nothing excluded; exactly one
+ *    NULL is an error.
+ *  - NaN factors are out of contract (no fault; the order among NaN scores is unspecified).
+ * Synchronous, on the engine's stream, after pending all-gathers. n_users == 0 or n_movies == 0: ALS_OK, outputs
+ * untouched. Uses a grow-only workspace of its own: a call between two chunks of one half leaves the half's prepared
+ * pre-split table and partial slots intact. */
+int als_recommend(als_engine* e, const int64_t* user_rows, int64_t n_users, const int64_t* movie_rows, int64_t n_movies,
+                  int top_n, const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* host_idx, float* host_score);
+/* Launch shape als_recommend would choose: info[0] = users per workgroup tile, [1] = candidate segments S (> 1: partial
+ * lists per segment, merged by a second kernel), [2] = candidates per segment, [3] = dynamic LDS bytes per workgroup. */
+int als_recommend_plan(const als_engine* e, int64_t n_users, int64_t n_movies, int top_n, int64_t info[4]);
+
 /* Sum of (r - x_row . y_col)^2 over the block's observed ratings and their count (the RMSE/MSE
  * reduction of scripts/calculate_mse.py:78-90 computed on the device from the factors). Synchronous. */
 int als_sq_error(als_engine* e, int side, double* sum_sq_error, int64_t* count);

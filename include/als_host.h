@@ -108,6 +108,11 @@ int als_write_prediction_csv(const char* path, const float* U, int64_t n_users, 
 /* The same file from a prediction matrix already computed (e.g. on the GPU by als_predict): P row-major
  * n_users x n_movies. */
 int als_write_prediction_matrix_csv(const char* path, const float* P, int64_t n_users, int64_t n_movies);
+/* Top-N lists (als_recommend) as text: one line "userId,movieId,score" per (user, rank j), users in the order given,
+ * best first; movie_ids / scores row-major n_users x top_n in raw ids, entries with movie id < 0 (padding) omitted.
+ * The score is printed as the prediction CSV prints a cell (Double.toString of the widened float). */
+int als_write_recommendations_csv(const char* path, const int64_t* user_ids, int64_t n_users, int top_n,
+                                  const int64_t* movie_ids, const float* scores);
 
 /* ---- Kafka wire formats (big-endian, as the reference's serializers write them) ----
  * FeatureMessage = i32 id | i32 n_deps | n_deps x i32 dependent id | i32 num_features | num_features x f32

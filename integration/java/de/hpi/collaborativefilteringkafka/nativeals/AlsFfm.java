@@ -80,6 +80,9 @@ public final class AlsFfm {
     // ---- collector, MSE, synchronisation (als.h:153-166)
     static final MethodHandle PREDICT = h("als_predict",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS));
+    static final MethodHandle RECOMMEND = h("als_recommend",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, JAVA_INT, ADDRESS, ADDRESS,
+                    ADDRESS, ADDRESS));
     static final MethodHandle SQ_ERROR = h("als_sq_error",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, ADDRESS));
     static final MethodHandle SYNCHRONIZE = h("als_synchronize", FunctionDescriptor.of(JAVA_INT, ADDRESS));
@@ -229,6 +232,39 @@ public final class AlsFfm {
             check("als_predict", (int) PREDICT.invokeExact(e, a.allocateFrom(JAVA_LONG, userRows),
                     (long) userRows.length, a.allocateFrom(JAVA_LONG, movieRows), (long) movieRows.length, out));
             return out.toArray(JAVA_FLOAT);
+        } catch (Throwable t) {
+            throw rethrow(t);
+        }
+    }
+
+    /**
+     * als_recommend: per query user the topN best-scoring candidates (positions in movieRows, best first, ties toward
+     * the smaller position) that are not excluded, scored exactly as predict scores a cell; the dense matrix is never
+     * formed. exclPtr / exclIdx: CSR of excluded candidate positions per query user (ascending), or both null.
+     * outIdx / outScore: userRows.length * topN each, row-major; -1 / -Infinity where a user has fewer candidates.
+     */
+    public static void recommend(MemorySegment e, long[] userRows, long[] movieRows, int topN, long[] exclPtr,
+                                 int[] exclIdx, int[] outIdx, float[] outScore) {
+        if ((exclPtr == null) != (exclIdx == null))
+            throw new IllegalArgumentException("recommend: exclPtr and exclIdx must both be given or both be null");
+        if (exclPtr != null && exclPtr.length != userRows.length + 1)
+            throw new IllegalArgumentException("recommend: exclPtr.length must be userRows.length + 1");
+        long cells = (long) userRows.length * Math.max(topN, 0);
+        if (outIdx.length != cells)
+            throw new IllegalArgumentException("recommend: outIdx.length must be userRows.length * topN");
+        if (outScore.length != cells)
+            throw new IllegalArgumentException("recommend: outScore.length must be userRows.length * topN");
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment idx = a.allocate(JAVA_INT, Math.max(cells, 1));
+            MemorySegment score = a.allocate(JAVA_FLOAT, Math.max(cells, 1));
+            MemorySegment ptr = exclPtr == null ? MemorySegment.NULL : a.allocateFrom(JAVA_LONG, exclPtr);
+            MemorySegment pos = exclIdx == null ? MemorySegment.NULL
+                    : exclIdx.length == 0 ? a.allocate(JAVA_INT, 1) : a.allocateFrom(JAVA_INT, exclIdx);
+            check("als_recommend", (int) RECOMMEND.invokeExact(e, a.allocateFrom(JAVA_LONG, userRows),
+                    (long) userRows.length, a.allocateFrom(JAVA_LONG, movieRows), (long) movieRows.length, topN, ptr, pos,
+                    idx, score));
+            MemorySegment.copy(idx, JAVA_INT, 0, outIdx, 0, outIdx.length);
+            MemorySegment.copy(score, JAVA_FLOAT, 0, outScore, 0, outScore.length);
         } catch (Throwable t) {
             throw rethrow(t);
         }

@@ -59,6 +59,29 @@ public final class AlsNative {
     public static native void allgatherShard(long engine, int side, long slotsPerChunk, long chunk);
     /** als_predict: out[u * movieRows.length + m] = U[userRows[u]] . M[movieRows[m]] as a Java float dot. */
     public static native void predict(long engine, long[] userRows, long[] movieRows, float[] out);
+    /**
+     * als_recommend: per query user the topN (1..64) best-scoring candidates that are not excluded, as positions into
+     * movieRows, best first, equal scores toward the smaller position; scored exactly as predict scores a cell, without
+     * the dense matrix. exclPtr / exclIdx: CSR of excluded candidate positions per query user (strictly ascending per
+     * user), or both null. outIdx / outScore: userRows.length * topN each, row-major; -1 / -Infinity where a user has
+     * fewer eligible candidates. Synchronising. The lengths are checked here (and again in the shim).
+     */
+    public static void recommend(long engine, long[] userRows, long[] movieRows, int topN, long[] exclPtr,
+                                 int[] exclIdx, int[] outIdx, float[] outScore) {
+        if ((exclPtr == null) != (exclIdx == null))
+            throw new IllegalArgumentException("recommend: exclPtr and exclIdx must both be given or both be null");
+        if (exclPtr != null && exclPtr.length != userRows.length + 1)
+            throw new IllegalArgumentException("recommend: exclPtr.length must be userRows.length + 1");
+        long cells = (long) userRows.length * Math.max(topN, 0);
+        if (outIdx.length != cells)
+            throw new IllegalArgumentException("recommend: outIdx.length must be userRows.length * topN");
+        if (outScore.length != cells)
+            throw new IllegalArgumentException("recommend: outScore.length must be userRows.length * topN");
+        recommend0(engine, userRows, movieRows, topN, exclPtr, exclIdx, outIdx, outScore);
+    }
+    /** The native of recommend (integration/jni/cfk_als_jni_recommend.c); called through recommend only. */
+    private static native void recommend0(long engine, long[] userRows, long[] movieRows, int topN, long[] exclPtr,
+                                          int[] exclIdx, int[] outIdx, float[] outScore);
     /** als_write_prediction_matrix_csv: EJML saveDenseCSV layout (FeatureCollector.java:103-106). */
     public static native void writePredictionMatrixCsv(String path, float[] prediction, long nUsers, long nMovies);
 }

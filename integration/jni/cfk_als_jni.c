@@ -276,3 +276,6 @@ JNIEXPORT void JNICALL Java_de_hpi_collaborativefilteringkafka_nativeals_AlsNati
     (*env)->ReleaseStringUTFChars(env, path, cpath);
     fail_status(env, "als_write_prediction_matrix_csv", st);
 }
+
+/* AlsNative.recommend's native (als_recommend): a file of its own that uses the helpers above */
+#include "cfk_als_jni_recommend.c"
