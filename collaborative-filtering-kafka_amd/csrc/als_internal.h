@@ -25,7 +25,7 @@ struct SolveArgs {
     int32_t flags;          // SOLVE_FLAG_* (diagnostics only; 0 in production)
     const void* opp_split;  // MFMA_SPLIT + presplit: the opposite table as fp16 h/m planes (als_presplit)
     uint32_t gen;           // launch generation (PARTIAL and its REDUCE share it): keys the partial-slot encoding
-    uint32_t* integrity;    // device record of partial slots that failed their check (see als_kernels.hip)
+    uint32_t* integrity;    // device record of partial slots that failed their check (see als_slots.h)
     float refine_min_pivot; // MFMA tile solve: skip the refinement step when every scaled pivot >= this (> 1: never)
     const uint32_t* rat_pk; // presplit: the padded ratings r = rh + rm as fp16 pairs (entries 2i, 2i+1): the rh pairs,
                             //   then (at rat_lo_off words) the rm pairs; both exact for every Java short
@@ -91,7 +91,7 @@ hipError_t launch_solve(int precision, int kp, Path path, const SolveArgs& a, hi
 // Block permutation of the in-block (32-entry blocks): dst block i <- src block perm[i] (cols and ratings).
 hipError_t launch_permute_blocks(const int32_t* col, const float* rat, int32_t* col_out, float* rat_out,
                                  const int32_t* perm, int64_t n_blocks, hipStream_t s);
-// Short rows in entry space (als_solve_dual): fp32 split path, kp 64 with cd 2, kp 128 with cd 2 or 4 (rows of
+// Short rows in entry space (als_solve_dual): fp32 split path, kp 64 with cd 2, kp 128 with cd 2, 4 or 6 (rows of
 // 16 * cd padded entries, i.e. cd / 2 blocks); `a.tasks` are FULL tasks of such rows.
 hipError_t launch_dual(int kp, int cd, const SolveArgs& a, hipStream_t s);
 // Pre-split of an fp32 [n_rows][kp] factor table (kp = 64 or 128, sentinel row included) into the two fp16 terms
@@ -99,7 +99,7 @@ hipError_t launch_dual(int kp, int cd, const SolveArgs& a, hipStream_t s);
 // two planes (h, m) of 2 kp bytes, plane position 16 b + j (b = 0..kp/16-1, j = 0..15) holding feature (kp/16) j + b
 // scaled by 2^s, so the 16 values one transposed LDS read hands to a 16-lane group (features (kp/16) j + b,
 // j = 0..15) are 32 contiguous bytes. launch_absmax writes the table's range statistics to amax[0..1] first (zeroed
-// here, on the stream); the presplit kernel and the Gram derive s from it (als_kernels.hip, split_exp).
+// here, on the stream); the presplit kernel and the Gram derive s from it (als_mfma.h, split_exp).
 hipError_t launch_absmax(const float* src, int64_t n_floats, int kp, uint32_t* amax /* 2 words */, hipStream_t s);
 hipError_t launch_presplit(int kp, const float* src, void* dst, int64_t n_rows, const uint32_t* amax, hipStream_t s);
 // padded column indices -> the per-block order of the presplit gather (n_entries = nnz_padded)

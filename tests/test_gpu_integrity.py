@@ -1,6 +1,6 @@
 """GPU: the split-row hand-off check (PARTIAL -> REDUCE partial slots) and the reference's full rating range.
 
-- Every partial slot is stored keyed by its launch generation with a check word (SlotCodec, als_kernels.hip);
+- Every partial slot is stored keyed by its launch generation with a check word (SlotCodec, als_slots.h);
   a REDUCE task that reads a slot its PARTIAL task's writes have not reached -- including a slot left over
   from an earlier launch with identical numbers -- fails the check and the engine's next synchronising call
   returns ALS_ERR_INTEGRITY.

@@ -394,7 +394,7 @@ def test_bitwise_determinism_netflix_shape(cfk):
     """Full Netflix-shape workload (1e8 ratings, k = 64, pre-split fp16 Gram on both halves, split rows): each half
     repeated from identical inputs -- with the other half run in between, which reuses the shared partial-slot and
     pre-split workspaces -- gives bitwise identical factors. (This is the test that caught an MFMA operand hazard at
-    ~20 rows in 17,770; see MFMA_DRAIN in als_kernels.hip.) A failure reports each deviating row's kind (split or
+    ~20 rows in 17,770; see MFMA_DRAIN in als_mfma.h.) A failure reports each deviating row's kind (split or
     FULL) and its error against the fp64 restatement; slot-level diagnosis (a fixed launch generation) is the
     debug build's tools/split_diag.py."""
     ds = cfk.Dataset.synthetic_netflix(480_189, 17_770, 100_000_000, 0xA15, nthreads=16)

@@ -5,7 +5,7 @@ For every v_mfma instruction of one kernel, walk the following straight-line ins
 W wait states (one per instruction, N + 1 per s_nop N; MFMAs are skipped) and report a VALU / LDS / VMEM
 instruction whose destination overlaps the MFMA's SrcA/SrcB, or its SrcC when SrcC != vDst (a true WAR: the
 compiler treated the operand as read at issue). This is the pattern behind the split-Gram hazard fixed by
-MFMA_DRAIN (als_kernels.hip); the scan lists candidates, it does not prove a hazard.
+MFMA_DRAIN (als_mfma.h); the scan lists candidates, it does not prove a hazard.
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I <csrc> -S --cuda-device-only als_kernels.hip -o k.s
   python tools/mfma_hazard_scan.py k.s als_solve_mfmaILi64ELi2ELb1ELb0E [W=16]

@@ -2,7 +2,7 @@
 """What goes wrong in a nondeterministic split row (PARTIAL slot) of the Netflix-shape movie half.
 
 Repeats {write U0, movie half, copy partial slots} REPS times with a fixed launch generation (slots bitwise
-comparable), finds slots that differ from the majority, decodes them (SlotCodec, als_kernels.hip) into the
+comparable), finds slots that differ from the majority, decodes them (SlotCodec, als_slots.h) into the
 64 x 64 Gram + RHS they hold, and explains the difference D = G_bad - G_good:
   - which accumulator tiles / RHS words differ,
   - the rank of D,
@@ -51,7 +51,7 @@ def decode(words, slot, gen=1):
 
 
 def gram_of(plain):
-    """Accumulator layout (als_kernels.hip, C = 4): tile p = (b1 <= b2), lane (g, c), reg r holds
+    """Accumulator layout (MfmaAcc, als_mfma.h, C = 4): tile p = (b1 <= b2), lane (g, c), reg r holds
     G[4 * (4g + r) + b1][4c + b2]; RHS word NT*4 + b of lane (g, c) is the group-g part of feature 4c + b."""
     import numpy as np
     G = np.zeros((64, 64))
