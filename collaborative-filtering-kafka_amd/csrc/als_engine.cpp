@@ -128,11 +128,14 @@ struct als_engine {
     void* d_partials = nullptr;
     size_t partial_bytes = 0;
     int64_t generic_slabs = 0;      // generic path: Gram slabs in d_partials
-    void* d_split = nullptr;        // pre-split opposite table (cfk::launch_presplit), sized for the larger need
+    void* d_split = nullptr;        // pre-split opposite table (launch_presplit_prepare), sized for the larger need
     size_t split_bytes = 0;
-    uint32_t* d_amax = nullptr;     // bits of the pre-split table's largest |x| (cfk::launch_absmax): its scale
+    uint32_t* d_prep = nullptr;     // the preparation's device words: two sets of cfk::PREP_SET_WORDS (the range words
+                                    //   of the pre-split table, used in turn), then per side the exponent its opposite
+                                    //   table was last split at
+    int prep_set = 0;               // the set of the last preparation: SolveArgs::amax of the half it served
     void* d_rec = nullptr;          // als_recommend's own grow-only workspace (rows, exclusion CSR, partial and final
-    size_t rec_bytes = 0;           //   lists): never d_partials / d_split / d_amax, which a half in progress owns
+    size_t rec_bytes = 0;           //   lists): never d_partials / d_split / d_prep, which a half in progress owns
     void* h_stage = nullptr;        // pinned staging of als_write_factors / als_read_factors (copy kernels)
     size_t stage_bytes = 0;
     uint32_t* d_integrity = nullptr;   // cfk::INTEGRITY_WORDS: partial slots that failed their check
@@ -378,11 +381,16 @@ int als_engine_create(int device, int num_features, int precision, als_engine** 
     st = hipDeviceGetAttribute(&e->cu_count, hipDeviceAttributeMultiprocessorCount, device);
     if (st == hipSuccess) st = hipMalloc((void**)&e->d_integrity, cfk::INTEGRITY_WORDS * sizeof(uint32_t));
     if (st == hipSuccess) st = hipMemset(e->d_integrity, 0, cfk::INTEGRITY_WORDS * sizeof(uint32_t));
-    if (st == hipSuccess) st = hipMalloc((void**)&e->d_amax, 2 * sizeof(uint32_t));
+    {   // both sets of range words zero, no side split yet
+        uint32_t prep[2 * cfk::PREP_SET_WORDS + 2] = {};
+        prep[2 * cfk::PREP_SET_WORDS] = prep[2 * cfk::PREP_SET_WORDS + 1] = cfk::PREP_NO_EXP;
+        if (st == hipSuccess) st = hipMalloc((void**)&e->d_prep, sizeof(prep));
+        if (st == hipSuccess) st = hipMemcpy(e->d_prep, prep, sizeof(prep), hipMemcpyHostToDevice);
+    }
     if (st != hipSuccess) {
         (void)hipStreamDestroy(e->stream);
         (void)hipFree(e->d_integrity);
-        (void)hipFree(e->d_amax);
+        (void)hipFree(e->d_prep);
         delete e;
         return fail(ALS_ERR_DEVICE, "integrity record: %s", hipGetErrorString(st));
     }
@@ -402,7 +410,7 @@ int als_engine_destroy(als_engine* e) {
     (void)hipFree(e->d_rec);
     (void)hipHostFree(e->h_stage);
     (void)hipFree(e->d_integrity);
-    (void)hipFree(e->d_amax);
+    (void)hipFree(e->d_prep);
     for (auto& rec : e->pending)
         for (auto ev : rec.ev) (void)hipEventDestroy(ev);
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -571,7 +579,8 @@ int finish_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, in
     blk.ilv_rows = plan.ilv_rows;
     blk.ilv_tasks = plan.ilv_tasks;
     if (layout.presplit) {
-        // the pre-split copy of the opposite table (cfk::launch_presplit, once per half), sized for the larger side
+        // the pre-split copy of the opposite table (cfk::launch_presplit_prepare, once per half), sized for the
+        // larger side
         const int64_t sb = (n_opp_rows + 1) * (int64_t)cfk::presplit_row_bytes(e->kp);
         if ((size_t)sb > e->split_bytes) {
             (void)hipFree(e->d_split);
@@ -884,18 +893,20 @@ int launch_half(als_engine* e, int side, float lambda, const Task* tasks, int32_
     }
     if (b.layout.presplit) {
         // the opposite replica is the half's input and does not change between its chunks (als.h): chunk 0
-        // converts it, later chunks reuse the conversion
+        // converts it, later chunks reuse the conversion and its range words. The two sets of range words alternate
+        // per preparation: each preparation zeroes the other set, which the launches of the half before it read.
         if (first_chunk) {
-            const int64_t n_floats = (b.n_opp_rows + 1) * (int64_t)e->kp;
-            HIP_TRY(cfk::launch_absmax((const float*)opp.ptr, n_floats, e->kp, e->d_amax, e->stream));
-            HIP_TRY(cfk::launch_presplit(e->kp, (const float*)opp.ptr, e->d_split, b.n_opp_rows + 1, e->d_amax,
-                                         e->stream));
+            e->prep_set ^= 1;
+            HIP_TRY(cfk::launch_presplit_prepare(e->kp, (const float*)opp.ptr, e->d_split, b.n_opp_rows + 1,
+                                                 e->d_prep + e->prep_set * cfk::PREP_SET_WORDS,
+                                                 e->d_prep + (e->prep_set ^ 1) * cfk::PREP_SET_WORDS,
+                                                 e->d_prep + 2 * cfk::PREP_SET_WORDS + side, e->cu_count, e->stream));
         }
         a.opp_split = e->d_split;
         a.rat_pk = b.d_rat_pk;
         a.rat_lo_off = b.nnz_padded / 2;
         a.col_ps = b.d_col_ps;
-        a.amax = e->d_amax;
+        a.amax = e->d_prep + e->prep_set * cfk::PREP_SET_WORDS;
     }
     HIP_TRY(cfk::launch_solve(e->precision, e->kp, e->path, a, e->stream, b.layout.presplit, false));
     if (b.layout.presplit) {
@@ -904,6 +915,7 @@ int launch_half(als_engine* e, int side, float lambda, const Task* tasks, int32_
         cfk::SolveArgs f = a;
         f.presplit_fallback = 1;
         f.grid_cap = 4 * e->cu_count;
+        // (on the main stream: on the side stream, ahead of the entry-space launches, the step was slower)
         HIP_TRY(cfk::launch_solve(e->precision, e->kp, e->path, f, e->stream, false, false));
     }
     if (side_dual) HIP_TRY(hipStreamWaitEvent(e->side_stream, e->fork, 0));

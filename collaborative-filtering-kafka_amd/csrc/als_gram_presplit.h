@@ -19,7 +19,7 @@ __device__ __forceinline__ int gram_presplit(const SolveArgs& a, const Task& tk,
     constexpr int B = BLOCK_SUBSTEPS;
     const int g = lane >> 4, j = lane & 15;
     const int nblk = (tk.nsteps + B - 1) / B;
-    // Two-term fp16 Gram over a PRE-SPLIT opposite table (als_presplit, once per half: the scaled h/m fp16
+    // Two-term fp16 Gram over a PRE-SPLIT opposite table (launch_presplit_prepare, once per half: the scaled h/m fp16
     // terms of every factor row, split2). Tile (b1, b2) takes hh + hm + mh (3 MFMAs), a diagonal tile hh + E
     // with E = h m^T folded as E + E^T once per task (2 MFMAs). The RHS Y^T r is 2 MFMAs per feature block on
     // B[k][c] = rh_k (columns 0-7) / rm_k (columns 8-15), r = rh + rm exact in fp16 for every Java short:

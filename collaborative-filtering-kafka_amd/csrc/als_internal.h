@@ -23,7 +23,7 @@ struct SolveArgs {
     float lambda;
     int32_t sentinel;       // index of the opposite side's all-zero sentinel row (= n_opp_rows)
     int32_t flags;          // SOLVE_FLAG_* (diagnostics only; 0 in production)
-    const void* opp_split;  // MFMA_SPLIT + presplit: the opposite table as fp16 h/m planes (als_presplit)
+    const void* opp_split;  // MFMA_SPLIT + presplit: the opposite table as fp16 h/m planes (launch_presplit_prepare)
     uint32_t gen;           // launch generation (PARTIAL and its REDUCE share it): keys the partial-slot encoding
     uint32_t* integrity;    // device record of partial slots that failed their check (see als_slots.h)
     float refine_min_pivot; // MFMA tile solve: skip the refinement step when every scaled pivot >= this (> 1: never)
@@ -34,7 +34,7 @@ struct SolveArgs {
     int32_t rows_per_chunk; // chunk-major slots (als_set_row_layout): 0 = factor row row_offset + row, else
     int64_t chunk_stride;   //   row_offset + (row / rows_per_chunk) * chunk_stride + row % rows_per_chunk
     int64_t rat_lo_off;     // presplit: words from the rh pairs to the rm pairs (nnz_padded / 2)
-    const uint32_t* amax;   // presplit: range statistics of the opposite table (als_absmax): [0] bits of its largest
+    const uint32_t* amax;   // presplit: range statistics of the opposite table (als_presplit_scan): [0] bits of its largest
                             //   |x| (the split scale), [1] ~bits of its smallest nonzero row maximum
     int32_t presplit_fallback;  // the on-the-fly split launch guarding a pre-split half: it runs only when the table
                                 //   is out of the pre-split's range (presplit_ok(amax) false), else exits at once
@@ -98,10 +98,19 @@ hipError_t launch_dual(int kp, int cd, const SolveArgs& a, hipStream_t s);
 // the presplit Gram stages in LDS: row r = presplit_row_bytes(kp) = 4 kp bytes (the fp32 row's size) at r * 4 kp =
 // two planes (h, m) of 2 kp bytes, plane position 16 b + j (b = 0..kp/16-1, j = 0..15) holding feature (kp/16) j + b
 // scaled by 2^s, so the 16 values one transposed LDS read hands to a 16-lane group (features (kp/16) j + b,
-// j = 0..15) are 32 contiguous bytes. launch_absmax writes the table's range statistics to amax[0..1] first (zeroed
-// here, on the stream); the presplit kernel and the Gram derive s from it (als_mfma.h, split_exp).
-hipError_t launch_absmax(const float* src, int64_t n_floats, int kp, uint32_t* amax /* 2 words */, hipStream_t s);
-hipError_t launch_presplit(int kp, const float* src, void* dst, int64_t n_rows, const uint32_t* amax, hipStream_t s);
+// j = 0..15) are 32 contiguous bytes, with s = split_exp (als_mfma.h) of the table's largest |x|.
+// One preparation is two launches on `s`. als_presplit_scan reads the table once: it splits it at the exponent *pred
+// (the one this side's table was last split at) and accumulates the table's range words into set[0..1] (as
+// SolveArgs::amax reads them). als_presplit_confirm then compares split_exp(set[0]) with the exponent used; only when
+// they differ (or *pred was PREP_NO_EXP) it splits the table again, at the true exponent. It stores that exponent to
+// *pred and zeroes next_set[0..1], the set of the next preparation. So dst is always the table split at the
+// split_exp of its own maximum, and nothing is read back to the host. set, next_set: PREP_SET_WORDS device words each,
+// zeroed once when allocated and then only through next_set, used in turn; cu_count caps both grids.
+constexpr int PREP_SET_WORDS = 4;            // [0], [1] the range words, [PREP_EXP] the exponent the scan split at
+constexpr int PREP_EXP = 2;
+constexpr uint32_t PREP_NO_EXP = 0x7fffffffu;   // *pred before a side's first preparation (no split_exp value)
+hipError_t launch_presplit_prepare(int kp, const float* src, void* dst, int64_t n_rows, uint32_t* set,
+                                   uint32_t* next_set, uint32_t* pred, int cu_count, hipStream_t s);
 // padded column indices -> the per-block order of the presplit gather (n_entries = nnz_padded)
 hipError_t launch_pack_cols_ps(const int32_t* col, int32_t* dst, int64_t n_entries, hipStream_t s);
 // padded fp32 ratings r -> fp16 pairs of rh = f16(r) at dst[0, n_pairs) and of rm = r - rh at dst[n_pairs, 2 n_pairs)

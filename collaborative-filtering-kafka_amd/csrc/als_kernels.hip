@@ -44,44 +44,8 @@ template <int KP>
 constexpr int mfma_waves() { return WAVES; }
 
 // Range statistics of a table for the pre-split Gram, from the bits of |x| (non-negative floats order as unsigned
-// integers): out[0] = the largest |x| (the split scale, split_exp), out[1] = ~(the smallest nonzero row maximum) (a
-// max of complements is a min; 0 = no nonzero row). Grid-stride over 16-B vectors, vpr vectors per row (a row's
-// vectors are consecutive lanes of one wave: the grid stride is a multiple of 64), workgroup reduction, one
-// vector-memory atomicMax per workgroup and word. out[0..1] are zeroed before the launch.
-__global__ __launch_bounds__(256) void als_absmax(const u32x4* __restrict__ src, int64_t n4, int vpr,
-                                                  uint32_t* __restrict__ out) {
-    uint32_t m = 0, rmin = 0xffffffffu;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i0 = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); i0 < n4; i0 += stride) {
-        const int64_t i = i0 + (threadIdx.x & 63);
-        uint32_t v = 0;
-        if (i < n4) {
-            const u32x4 x = src[i] & 0x7fffffffu;
-            v = max(max(x[0], x[1]), max(x[2], x[3]));
-        }
-        m = max(m, v);
-        for (int o = 1; o < vpr; o <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));   // the row's maximum
-        if (v != 0 && i < n4) rmin = min(rmin, v);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        m = max(m, (uint32_t)__shfl_xor((int)m, o));
-        rmin = min(rmin, (uint32_t)__shfl_xor((int)rmin, o));
-    }
-    // one atomic per workgroup: thousands of same-address atomics serialise (53 us for the 4.5 MB M table)
-    __shared__ uint32_t wm[4], wr[4];
-    if ((threadIdx.x & 63) == 0) {
-        wm[threadIdx.x >> 6] = m;
-        wr[threadIdx.x >> 6] = rmin;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(wm[0], wm[1]), max(wm[2], wm[3]));
-        rmin = min(min(wr[0], wr[1]), min(wr[2], wr[3]));
-        if (m != 0) atomicMax(out, m);
-        if (rmin != 0xffffffffu) atomicMax(out + 1, ~rmin);
-    }
-}
+// integers): word 0 = the largest |x| (the split scale, split_exp), word 1 = ~(the smallest nonzero row maximum) (a
+// max of complements is a min; 0 = no nonzero row). als_presplit_scan accumulates them while it splits the table.
 // The pre-split (table-wide scale, two fp16 terms) keeps ~22 significant bits for values within 2^-17 of the table's
 // largest |x| and falls toward the fp16 subnormal floor below; it serves a half only when every nonzero row's
 // maximum is within PRESPLIT_RANGE of the table's. Otherwise that half's Gram runs on the fp32 table with the
@@ -95,29 +59,102 @@ __device__ __forceinline__ bool presplit_ok(const uint32_t* st) {
     return __uint_as_float(mx) <= PRESPLIT_RANGE * __uint_as_float(~rc);
 }
 
-// fp32 table -> fp16 h/m planes (presplit_row_bytes(KP) per row, als_internal.h) at the table's scale 2^s: thread
-// (row, b, jh) splits features C (8 jh + i) + b, i = 0..7, and writes 16 B per plane at plane position 16 b + 8 jh.
+// fp32 table -> fp16 h/m planes (presplit_row_bytes(KP) per row, als_internal.h) at the scale 2^sc: item t = (row, b,
+// jh) splits features C (8 jh + i) + b, i = 0..7, and writes 16 B per plane at plane position 16 b + 8 jh. Returns the
+// bits of the largest |x| of its eight values.
 template <int KP>
-__global__ __launch_bounds__(256) void als_presplit(const float* __restrict__ src, unsigned* __restrict__ dst,
-                                                   int64_t n_threads, const uint32_t* __restrict__ amax) {
+__device__ __forceinline__ uint32_t presplit_item(const float* __restrict__ src, unsigned* __restrict__ dst, int64_t t,
+                                                  int sc) {
     constexpr int C = KP / 16;
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_threads) return;
-    const int sc = split_exp(*amax);
     const int64_t row = t / (2 * C);
     const int b = (int)(t % (2 * C)) >> 1, jh = (int)(t & 1);
     const float* s = src + row * KP + C * 8 * jh + b;
+    float x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = s[C * i];
     u32x4 h, m;
+    uint32_t v = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         unsigned hh, mm;
-        split2(ldexpf(s[C * (2 * i)], sc), ldexpf(s[C * (2 * i + 1)], sc), hh, mm);
+        split2(ldexpf(x[2 * i], sc), ldexpf(x[2 * i + 1], sc), hh, mm);
         h[i] = hh;
         m[i] = mm;
+        v = max(v, max(__float_as_uint(x[2 * i]) & 0x7fffffffu, __float_as_uint(x[2 * i + 1]) & 0x7fffffffu));
     }
     unsigned* o = dst + row * (presplit_row_bytes(KP) / 4) + (16 * b + 8 * jh) / 2;
     *(u32x4*)o = h;
     *(u32x4*)(o + KP / 2) = m;   // plane stride 2 KP bytes
+    return v;
+}
+// The one pass of a table's preparation: splits the table at the PREDICTED exponent *pred (the exponent this side's
+// table was last split at; PREP_NO_EXP: none yet, any exponent does) and accumulates the range words of the same
+// values into set[0..1], which als_presplit_confirm zeroed after the preparation before last. Grid-stride over
+// 1024-thread workgroups; the 2 C items of a row are consecutive lanes of one wave (the stride is a multiple of 64);
+// workgroup reduction, at most one vector-memory atomicMax per workgroup and word (thousands of same-address atomics
+// serialise: 53 us for the 4.5 MB M table), none where the word already holds as much. set[PREP_EXP] <- *pred.
+template <int KP>
+__global__ __launch_bounds__(1024) void als_presplit_scan(const float* __restrict__ src, unsigned* __restrict__ dst,
+                                                         int64_t n_items, const uint32_t* __restrict__ pred,
+                                                         uint32_t* __restrict__ set) {
+    const uint32_t p = *pred;
+    const int sc = p == PREP_NO_EXP ? 0 : (int)p;
+    uint32_t m = 0, rmin = 0xffffffffu;
+    const int64_t stride = (int64_t)gridDim.x * 1024;
+    for (int64_t t0 = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63); t0 < n_items; t0 += stride) {
+        const int64_t t = t0 + (threadIdx.x & 63);
+        uint32_t v = t < n_items ? presplit_item<KP>(src, dst, t, sc) : 0;
+        m = max(m, v);
+#pragma unroll
+        for (int o = 1; o < 2 * (KP / 16); o <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));   // the row's maximum
+        if (v != 0 && t < n_items) rmin = min(rmin, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        m = max(m, (uint32_t)__shfl_xor((int)m, o));
+        rmin = min(rmin, (uint32_t)__shfl_xor((int)rmin, o));
+    }
+    __shared__ uint32_t wm[16], wr[16];
+    if ((threadIdx.x & 63) == 0) {
+        wm[threadIdx.x >> 6] = m;
+        wr[threadIdx.x >> 6] = rmin;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        m = threadIdx.x < 16 ? wm[threadIdx.x] : 0;
+        rmin = threadIdx.x < 16 ? wr[threadIdx.x] : 0xffffffffu;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+            m = max(m, (uint32_t)__shfl_xor((int)m, o));
+            rmin = min(rmin, (uint32_t)__shfl_xor((int)rmin, o));
+        }
+        if (threadIdx.x == 0) {
+            // the words only grow during the launch: a value read early can only ask for an atomic too many
+            if (m > __hip_atomic_load(set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(set, m);
+            if (~rmin > __hip_atomic_load(set + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(set + 1, ~rmin);
+            if (blockIdx.x == 0) set[PREP_EXP] = p;
+        }
+    }
+}
+// After the scan: the table's true exponent is split_exp of set[0]. Where the scan split at it (the prediction was
+// right, as it is unless the table's maximum crossed a power of two), every wave exits after its scalar loads; else
+// the capped grid strides over the table and splits it again at the true exponent. Either way thread 0 stores the
+// true exponent as the side's next prediction and zeroes the set the next preparation accumulates into (no launch
+// reads that one any more: the launches of the half it served precede this one on the stream).
+template <int KP>
+__global__ __launch_bounds__(256) void als_presplit_confirm(const float* __restrict__ src, unsigned* __restrict__ dst,
+                                                           int64_t n_items, const uint32_t* __restrict__ set,
+                                                           uint32_t* __restrict__ next_set, uint32_t* __restrict__ pred) {
+    const int sc = split_exp(set[0]);
+    const bool right = set[PREP_EXP] == (uint32_t)sc;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *pred = (uint32_t)sc;
+        next_set[0] = 0;
+        next_set[1] = 0;
+    }
+    if (right) return;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n_items; t += stride) presplit_item<KP>(src, dst, t, sc);
 }
 // In-block column indices in the order of the LDS-DMA gather: inside a 32-entry block, word 4 r + x (r = 0..7,
 // x = 0..3) holds the column of entry k = 16 (x >> 1) + 8 (r >> 2) + 4 (x & 1) + (r & 3), so the 8 lanes of loader
@@ -668,24 +705,25 @@ hipError_t launch_pack_ratings(const float* rat, uint32_t* dst, int64_t n_pairs,
     als_pack_ratings<<<(unsigned)((n_pairs + 255) / 256), 256, 0, s>>>(rat, dst, n_pairs);
     return hipGetLastError();
 }
-hipError_t launch_absmax(const float* src, int64_t n_floats, int kp, uint32_t* amax, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(amax, 0, 2 * sizeof(uint32_t), s);
-    if (e != hipSuccess || n_floats <= 0) return e;
-    if (n_floats % kp || kp % 4 || kp / 4 > 64 || (kp / 4 & (kp / 4 - 1))) return hipErrorInvalidValue;   // whole rows
-    const int64_t n4 = n_floats / 4;
-    // >= 8 vectors per thread, at most 512 workgroups (= atomics)
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n4 + 2047) / 2048, 512));
-    als_absmax<<<(unsigned)blocks, 256, 0, s>>>((const u32x4*)src, n4, kp / 4, amax);
+template <int KP>
+hipError_t launch_prepare_t(const float* src, void* dst, int64_t n_items, uint32_t* set, uint32_t* next_set,
+                            uint32_t* pred, int cu_count, hipStream_t s) {
+    const int cu = std::max(1, cu_count);
+    // the scan: two 1024-thread workgroups per CU fill it (8 waves per SIMD), so at most 2 cu atomics per word
+    const unsigned gs = (unsigned)std::min<int64_t>((n_items + 1023) / 1024, 2 * cu);
+    als_presplit_scan<KP><<<gs, 1024, 0, s>>>(src, (unsigned*)dst, n_items, pred, set);
+    // confirm / repair: a capped grid, as the range guard's fallback (its waves nearly always exit at once)
+    const unsigned gc = (unsigned)std::min<int64_t>((n_items + 255) / 256, 4 * cu);
+    als_presplit_confirm<KP><<<gc, 256, 0, s>>>(src, (unsigned*)dst, n_items, set, next_set, pred);
     return hipGetLastError();
 }
-hipError_t launch_presplit(int kp, const float* src, void* dst, int64_t n_rows, const uint32_t* amax, hipStream_t s) {
-    const int64_t threads = n_rows * 2 * (kp / 16);
-    if (threads <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((threads + 255) / 256);
-    if (kp == 64) als_presplit<64><<<grid, 256, 0, s>>>(src, (unsigned*)dst, threads, amax);
-    else if (kp == 128) als_presplit<128><<<grid, 256, 0, s>>>(src, (unsigned*)dst, threads, amax);
-    else return hipErrorInvalidValue;   // the pre-split Gram is built for KP = 64 and 128
-    return hipGetLastError();
+hipError_t launch_presplit_prepare(int kp, const float* src, void* dst, int64_t n_rows, uint32_t* set,
+                                   uint32_t* next_set, uint32_t* pred, int cu_count, hipStream_t s) {
+    if (n_rows <= 0) return hipErrorInvalidValue;   // the sentinel row is always there
+    const int64_t n_items = n_rows * 2 * (kp / 16);
+    if (kp == 64) return launch_prepare_t<64>(src, dst, n_items, set, next_set, pred, cu_count, s);
+    if (kp == 128) return launch_prepare_t<128>(src, dst, n_items, set, next_set, pred, cu_count, s);
+    return hipErrorInvalidValue;   // the pre-split Gram is built for KP = 64 and 128
 }
 hipError_t launch_pack_cols_ps(const int32_t* col, int32_t* dst, int64_t n_entries, hipStream_t s) {
     if (n_entries <= 0) return hipSuccess;

@@ -31,7 +31,7 @@ __device__ __forceinline__ f32x4 mfma_k32(const u32x4& a, const u32x4& b, f32x4 
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a), as_bf16x8(b), c, 0, 0, 0);
 }
 
-// Two-term fp16 split of the pre-split tables (als_presplit): x' = x 2^s (s = split_exp of the table's largest |x|,
+// Two-term fp16 split of the pre-split tables (als_presplit_scan): x' = x 2^s (s = split_exp of the table's largest |x|,
 // so |x'| <= 2^14), h = f16_rn(x'), m = f16_rn(x' - h). x' - h is exact in fp32 and |x' - h - m| <= 2^-22 |x'|, so
 // h + m carries 22 significant bits of every value. A product is taken as hh + hm + mh (the dropped mm and the
 // representation error are <= 3 2^-22 |x'y'|); every fp16 x fp16 partial product is exact in the fp32 MFMA
@@ -51,7 +51,7 @@ __device__ __forceinline__ f32x4 mfma_f16(const u32x4& a, const u32x4& b, f32x4 
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
                                                   0);
 }
-// Scale exponent s of a pre-split table from the bits of its largest |x| (als_absmax): 2^s max|x| <= 2^14 < the fp16
+// Scale exponent s of a pre-split table from the bits of its largest |x| (als_presplit_scan): 2^s max|x| <= 2^14 < the fp16
 // maximum 65504 (no overflow at any rounding), and the table's values use the whole fp16 range (m stays normal for
 // |x| >= 2^-17 max|x|). A zero, infinite or NaN maximum keeps s = 0; s is clamped so 2^s and 2^-2s stay usable.
 __device__ __forceinline__ int split_exp(uint32_t maxbits) {

@@ -103,7 +103,7 @@ BlockLayout plan_layout(const PlanKnobs& kn, const BlockShape& s, const std::vec
     const int64_t sb = presplit_table_bytes(s);
     L.ranges = L.ilv > 0 && s.n_opp_rows > 0 &&
                (kn.xcd_ranges > 0 || (kn.xcd_ranges < 0 && s.kp == 64 && sb <= (128ll << 20)));
-    // Pre-split opposite table (scaled two-term fp16, cfk::launch_presplit, once per half) for the MFMA Gram: 4 KP
+    // Pre-split opposite table (scaled two-term fp16, cfk::launch_presplit_prepare, once per half) for the MFMA Gram: 4 KP
     // bytes per row (the fp32 row's size), 3 MFMAs per tile instead of the on-the-fly bf16 split's 6, no split VALU
     // (the rows reach LDS by DMA and the MFMA operands come back with transposed reads). Chosen where the Gram is
     // MFMA-bound: always at KP = 128, and at KP = 64 for a cache-resident opposite table (<= 8 MB: the 17,770-row

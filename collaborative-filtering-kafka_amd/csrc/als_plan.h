@@ -56,7 +56,7 @@ static_assert(sizeof(Task) == 32, "Task layout");
 // the Gram's packed lower triangle in LDS (or a per-workgroup global slab) and a workgroup Cholesky.
 enum class Path : int { VALU = 0, MFMA = 1, MFMA_SPLIT = 2, GENERIC = 3 };
 
-// Bytes of one row of the pre-split opposite table (als_internal.h, launch_presplit): the fp32 row's size.
+// Bytes of one row of the pre-split opposite table (als_internal.h, launch_presplit_prepare): the fp32 row's size.
 CFK_HOST_DEVICE constexpr int presplit_row_bytes(int kp) { return 4 * kp; }
 
 // Everything the environment can say about the plan (read once per engine by the engine's read_environment, which
