@@ -58,27 +58,20 @@ unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 int build_block_device(const int32_t* rows, const int32_t* cols, const int16_t* ratings, int64_t nnz, int64_t n_rows,
                        int64_t n_opp_rows, hipStream_t s, std::vector<int64_t>& deg, std::vector<int64_t>& begin,
-                       int32_t** d_col_out, float** d_rat_out, std::string& err) {
-    *d_col_out = nullptr;
-    *d_rat_out = nullptr;
+                       DeviceBuf<int32_t>& d_col_out, DeviceBuf<float>& d_rat_out, std::string& err) {
+    d_col_out.reset();
+    d_rat_out.reset();
     deg.assign(n_rows, 0);
     begin.assign(n_rows + 1, 0);
-    int32_t *d_rows = nullptr, *d_cols = nullptr, *d_idx = nullptr, *d_rows_s = nullptr, *d_idx_s = nullptr;
-    int32_t *d_end = nullptr, *d_col = nullptr;
-    int16_t* d_r16 = nullptr;
-    float* d_rat = nullptr;
-    int64_t *d_start = nullptr, *d_begin = nullptr;
-    unsigned* d_bad = nullptr;
-    void* d_tmp = nullptr;
-    auto release = [&](bool keep_out) {
-        for (void* p : {(void*)d_rows, (void*)d_cols, (void*)d_idx, (void*)d_rows_s, (void*)d_idx_s, (void*)d_end,
-                        (void*)d_r16, (void*)d_start, (void*)d_begin, (void*)d_bad, d_tmp})
-            (void)hipFree(p);
-        if (!keep_out) {
-            (void)hipFree(d_col);
-            (void)hipFree(d_rat);
-        }
-    };
+    // every buffer is released when the function returns (last declared first: d_rows, d_cols, ... d_tmp, the order
+    // of the hand-written clean-up this replaces); d_col / d_rat are handed over on success
+    DeviceBuf<int32_t> d_col;
+    DeviceBuf<float> d_rat;
+    DeviceBuf<char> d_tmp;
+    DeviceBuf<unsigned> d_bad;
+    DeviceBuf<int64_t> d_begin, d_start;
+    DeviceBuf<int16_t> d_r16;
+    DeviceBuf<int32_t> d_end, d_idx_s, d_rows_s, d_idx, d_cols, d_rows;
     hipError_t st = hipSuccess;
     auto ok = [&](hipError_t e, const char* what) {
         if (e != hipSuccess && st == hipSuccess) {
@@ -87,66 +80,54 @@ int build_block_device(const int32_t* rows, const int32_t* cols, const int16_t* 
         }
         return st == hipSuccess;
     };
-    const size_t n4 = (size_t)nnz * 4;
+    const char* const ALLOC = "device allocation";
+    const size_t n = (size_t)nnz, n4 = n * 4;
     if (nnz > 0) {
-        if (!ok(hipMalloc((void**)&d_rows, n4), "hipMalloc") || !ok(hipMalloc((void**)&d_cols, n4), "hipMalloc") ||
-            !ok(hipMalloc((void**)&d_r16, (size_t)nnz * 2), "hipMalloc") || !ok(hipMalloc((void**)&d_idx, n4), "hipMalloc") ||
-            !ok(hipMalloc((void**)&d_rows_s, n4), "hipMalloc") || !ok(hipMalloc((void**)&d_idx_s, n4), "hipMalloc") ||
-            !ok(hipMalloc((void**)&d_bad, sizeof(unsigned)), "hipMalloc")) {
-            release(false);
+        if (!ok(d_rows.alloc(n), ALLOC) || !ok(d_cols.alloc(n), ALLOC) || !ok(d_r16.alloc(n), ALLOC) ||
+            !ok(d_idx.alloc(n), ALLOC) || !ok(d_rows_s.alloc(n), ALLOC) || !ok(d_idx_s.alloc(n), ALLOC) ||
+            !ok(d_bad.alloc(1), ALLOC))
             return ALS_ERR_OUT_OF_MEMORY;
-        }
-        ok(hipMemcpyAsync(d_rows, rows, n4, hipMemcpyHostToDevice, s), "upload");
-        ok(hipMemcpyAsync(d_cols, cols, n4, hipMemcpyHostToDevice, s), "upload");
-        ok(hipMemcpyAsync(d_r16, ratings, (size_t)nnz * 2, hipMemcpyHostToDevice, s), "upload");
-        ok(hipMemsetAsync(d_bad, 0, sizeof(unsigned), s), "memset");
+        ok(hipMemcpyAsync(d_rows.get(), rows, n4, hipMemcpyHostToDevice, s), "upload");
+        ok(hipMemcpyAsync(d_cols.get(), cols, n4, hipMemcpyHostToDevice, s), "upload");
+        ok(hipMemcpyAsync(d_r16.get(), ratings, n * 2, hipMemcpyHostToDevice, s), "upload");
+        ok(hipMemsetAsync(d_bad.get(), 0, sizeof(unsigned), s), "memset");
         if (st == hipSuccess) {
-            validate_iota<<<grid_for(nnz), 256, 0, s>>>(d_rows, d_cols, nnz, n_rows, n_opp_rows, d_idx, d_bad);
+            validate_iota<<<grid_for(nnz), 256, 0, s>>>(d_rows.get(), d_cols.get(), nnz, n_rows, n_opp_rows, d_idx.get(),
+                                                        d_bad.get());
             ok(hipGetLastError(), "validate");
         }
         unsigned bad = 0;
-        ok(hipMemcpyAsync(&bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, s), "download");
+        ok(hipMemcpyAsync(&bad, d_bad.get(), sizeof(unsigned), hipMemcpyDeviceToHost, s), "download");
         ok(hipStreamSynchronize(s), "sync");
-        if (st != hipSuccess) {
-            release(false);
-            return ALS_ERR_DEVICE;
-        }
+        if (st != hipSuccess) return ALS_ERR_DEVICE;
         if (bad) {
             err = (bad & 1) ? "a row index is outside [0, n_rows)" : "a column index is outside [0, n_opp_rows)";
-            release(false);
             return ALS_ERR_INVALID_ARGUMENT;
         }
         // stable LSD radix sort of (row, arrival index) over the bits the row count needs
         int end_bit = 1;
         while (end_bit < 31 && ((int64_t)1 << end_bit) < n_rows) ++end_bit;
         size_t tmp_bytes = 0;
-        ok(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_rows, d_rows_s, d_idx, d_idx_s, (int)nnz, 0, end_bit, s),
+        ok(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_rows.get(), d_rows_s.get(), d_idx.get(), d_idx_s.get(),
+                                              (int)nnz, 0, end_bit, s),
            "radix sort sizing");
-        if (st == hipSuccess && !ok(hipMalloc(&d_tmp, tmp_bytes), "hipMalloc")) {
-            release(false);
-            return ALS_ERR_OUT_OF_MEMORY;
-        }
-        ok(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_rows, d_rows_s, d_idx, d_idx_s, (int)nnz, 0, end_bit, s),
+        if (st == hipSuccess && !ok(d_tmp.alloc(tmp_bytes), ALLOC)) return ALS_ERR_OUT_OF_MEMORY;
+        ok(hipcub::DeviceRadixSort::SortPairs(d_tmp.get(), tmp_bytes, d_rows.get(), d_rows_s.get(), d_idx.get(),
+                                              d_idx_s.get(), (int)nnz, 0, end_bit, s),
            "radix sort");
         // inclusive end of every non-empty row's run -> degrees on the host
         std::vector<int32_t> ends(n_rows, -1);
         if (st == hipSuccess && n_rows > 0) {
-            if (!ok(hipMalloc((void**)&d_end, (size_t)n_rows * 4), "hipMalloc")) {
-                release(false);
-                return ALS_ERR_OUT_OF_MEMORY;
-            }
-            ok(hipMemsetAsync(d_end, 0xff, (size_t)n_rows * 4, s), "memset");
+            if (!ok(d_end.alloc((size_t)n_rows), ALLOC)) return ALS_ERR_OUT_OF_MEMORY;
+            ok(hipMemsetAsync(d_end.get(), 0xff, d_end.bytes(), s), "memset");
             if (st == hipSuccess) {
-                row_degrees<<<grid_for(nnz), 256, 0, s>>>(d_rows_s, nnz, d_end);
+                row_degrees<<<grid_for(nnz), 256, 0, s>>>(d_rows_s.get(), nnz, d_end.get());
                 ok(hipGetLastError(), "row_degrees");
             }
-            ok(hipMemcpyAsync(ends.data(), d_end, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s), "download");
+            ok(hipMemcpyAsync(ends.data(), d_end.get(), d_end.bytes(), hipMemcpyDeviceToHost, s), "download");
             ok(hipStreamSynchronize(s), "sync");
         }
-        if (st != hipSuccess) {
-            release(false);
-            return ALS_ERR_DEVICE;
-        }
+        if (st != hipSuccess) return ALS_ERR_DEVICE;
         // rows are dense in [0, n_rows): start of row r = end of the previous non-empty row
         int64_t prev_end = 0;
         for (int64_t r = 0; r < n_rows; ++r) {
@@ -160,7 +141,6 @@ int build_block_device(const int32_t* rows, const int32_t* cols, const int16_t* 
     for (int64_t r = 0; r < n_rows; ++r) {
         if (deg[r] > INT32_MAX / 2) {
             err = "a row has more than 2^30 entries";
-            release(false);
             return ALS_ERR_UNSUPPORTED;
         }
         start[r + 1] = start[r] + deg[r];
@@ -168,33 +148,25 @@ int build_block_device(const int32_t* rows, const int32_t* cols, const int16_t* 
     }
     const int64_t padded = begin[n_rows];
     if (padded > 0) {
-        if (!ok(hipMalloc((void**)&d_col, (size_t)padded * 4), "hipMalloc") ||
-            !ok(hipMalloc((void**)&d_rat, (size_t)padded * 4), "hipMalloc") ||
-            !ok(hipMalloc((void**)&d_start, (size_t)(n_rows + 1) * 8), "hipMalloc") ||
-            !ok(hipMalloc((void**)&d_begin, (size_t)(n_rows + 1) * 8), "hipMalloc")) {
-            release(false);
+        if (!ok(d_col.alloc((size_t)padded), ALLOC) || !ok(d_rat.alloc((size_t)padded), ALLOC) ||
+            !ok(d_start.alloc(start.size()), ALLOC) || !ok(d_begin.alloc(begin.size()), ALLOC))
             return ALS_ERR_OUT_OF_MEMORY;
-        }
-        ok(hipMemcpyAsync(d_start, start.data(), (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, s), "upload");
-        ok(hipMemcpyAsync(d_begin, begin.data(), (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, s), "upload");
+        ok(hipMemcpyAsync(d_start.get(), start.data(), d_start.bytes(), hipMemcpyHostToDevice, s), "upload");
+        ok(hipMemcpyAsync(d_begin.get(), begin.data(), d_begin.bytes(), hipMemcpyHostToDevice, s), "upload");
         if (st == hipSuccess) {
-            fill_padding<<<grid_for(padded), 256, 0, s>>>(d_col, d_rat, padded, (int32_t)n_opp_rows);
+            fill_padding<<<grid_for(padded), 256, 0, s>>>(d_col.get(), d_rat.get(), padded, (int32_t)n_opp_rows);
             ok(hipGetLastError(), "fill");
         }
         if (st == hipSuccess && nnz > 0) {
-            scatter_block<<<grid_for(nnz), 256, 0, s>>>(d_rows_s, d_idx_s, d_cols, d_r16, nnz, d_start, d_begin, d_col,
-                                                        d_rat);
+            scatter_block<<<grid_for(nnz), 256, 0, s>>>(d_rows_s.get(), d_idx_s.get(), d_cols.get(), d_r16.get(), nnz,
+                                                        d_start.get(), d_begin.get(), d_col.get(), d_rat.get());
             ok(hipGetLastError(), "scatter");
         }
         ok(hipStreamSynchronize(s), "sync");
     }
-    if (st != hipSuccess) {
-        release(false);
-        return ALS_ERR_DEVICE;
-    }
-    release(true);
-    *d_col_out = d_col;
-    *d_rat_out = d_rat;
+    if (st != hipSuccess) return ALS_ERR_DEVICE;
+    d_col_out = std::move(d_col);
+    d_rat_out = std::move(d_rat);
     return ALS_OK;
 }
 

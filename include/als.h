@@ -83,7 +83,8 @@ int als_factor_stride(const als_engine* e);
  * MRatings2BlocksProcessor.java:48-69 / URatings2BlocksProcessor.java:72-92 fill: one CSR row per entity
  * of this partition, entries in in-block order. Row i is solved into factor row (row_offset + i) of
  * `side`; col_idx[] are rows of the opposite side's factor matrix (0 <= col < n_opp_rows).
- * Host pointers; copied to the device once. */
+ * Host pointers; copied to the device once. A failed als_set_block / als_set_block_coo leaves the side's previous
+ * block, chunks and row layout set and usable (only ALS_ERR_OUT_OF_MEMORY may unset the blocks of both sides). */
 int als_set_block(als_engine* e, int side, int64_t n_rows, int64_t row_offset, int64_t n_opp_rows,
                   const int64_t* row_ptr, const int32_t* col_idx, const int16_t* ratings);
 
@@ -124,7 +125,8 @@ int als_solve_half(als_engine* e, int side, float lambda);
  * RCCL while chunk c+1 is solved -- the per-partition fan-out of the reference's feature topics
  * (ALSApp.java:105-148) overlapped with compute. Replaces any previous chunking of that side. The chunks of
  * one half are solved in ascending order starting with chunk 0, and the opposite factor replica (the half's
- * input) does not change between them: chunk 0 prepares it (the pre-split copy), later chunks reuse that. */
+ * input) does not change between them: chunk 0 prepares it (the pre-split copy), later chunks reuse that. A failed
+ * als_set_chunks leaves the side's previous chunking as it was. */
 int als_set_chunks(als_engine* e, int side, int n_chunks, const int64_t* row_bounds);
 int als_solve_half_chunk(als_engine* e, int side, float lambda, int chunk);
 /* Chunk-major slot layout of `side`'s rows (after als_set_block, which resets it): local row i is solved into
