@@ -14,8 +14,9 @@ namespace {
 // over the rows. MFeatureCalculator.java:85-99 for that row: the Gram's lower triangle and the RHS accumulated over
 // LDS-staged batches of gathered factor rows, A + lambda n I (padded features: identity), a right-looking Cholesky
 // (one pivot column per step, the trailing update spread over the workgroup), forward and backward substitution.
-// G_LDS: the packed lower triangle lives in LDS (kp <= 256 fp32, <= 128 fp64); otherwise in a per-workgroup slab
-// of `scratch` (slab elements each). Not a benchmark configuration: correctness for every k (ALSAppRunner.java:18
+// G_LDS: the packed lower triangle lives in LDS while it and eight staged rows fit beside the static vectors below
+// (generic_plan, als_plan.cpp: kp <= 272 in fp32, <= 176 in fp64, where a batch is down to 10 and 15 rows); otherwise
+// in a per-workgroup slab of `scratch` (slab elements each). Not a benchmark configuration: correctness for every k (ALSAppRunner.java:18
 // accepts any NUM_FEATURES), at the cost of O(k^2) LDS traffic per gathered row.
 template <class T, bool G_LDS>
 __global__ __launch_bounds__(256) void als_solve_generic(SolveArgs a, int kp, int batch, T* __restrict__ scratch,
@@ -25,10 +26,15 @@ __global__ __launch_bounds__(256) void als_solve_generic(SolveArgs a, int kp, in
     const int64_t ntri = (int64_t)kp * (kp + 1) / 2;
     T* G = G_LDS ? (T*)gsmem : scratch + (int64_t)blockIdx.x * slab;   // packed lower triangle, tri(i, j)
     T* stage = (T*)gsmem + (G_LDS ? ((ntri + 1) & ~(int64_t)1) : 0); // batch x kp gathered rows
-    __shared__ T vec[1024 + 1];                                         // RHS / solution (kp <= 1024) + pivot
-    // fp64: the refinement step's residual / correction and per-entry residuals of a batch (batch <= 64)
-    __shared__ T res[std::is_same<T, double>::value ? 1024 : 1];
-    __shared__ T tb[std::is_same<T, double>::value ? 64 : 1];
+    constexpr bool F64 = std::is_same<T, double>::value;
+    __shared__ T vec[generic_vec_elems()];      // RHS / solution (kp <= GENERIC_MAX_KP) + pivot
+    // fp64: the refinement step's residual / correction and per-entry residuals of a batch (<= GENERIC_MAX_BATCH)
+    __shared__ T res[generic_res_elems(F64)];
+    __shared__ T tb[generic_tb_elems(F64)];
+    // what generic_plan leaves out of the dynamic LDS budget (the 16-byte aligned gsmem rounds the statics up)
+    static_assert(sizeof(vec) + sizeof(res) + sizeof(tb) <= (size_t)generic_static_lds_bytes(F64) &&
+                      (size_t)generic_static_lds_bytes(F64) < sizeof(vec) + sizeof(res) + sizeof(tb) + GENERIC_LDS_ALIGN,
+                  "generic_plan's static LDS is not this kernel's");
     const T* opp = (const T*)a.opp;
     auto tri_ = [](int64_t i, int64_t j) { return i * (i + 1) / 2 + j; };
     for (int task = blockIdx.x; task < a.n_tasks; task += gridDim.x) {
@@ -77,10 +83,10 @@ __global__ __launch_bounds__(256) void als_solve_generic(SolveArgs a, int kp, in
             if (tid == 0) {
                 const T d = sqrt(G[tri_(j, j)]);
                 G[tri_(j, j)] = d;
-                vec[1024] = d;
+                vec[GENERIC_MAX_KP] = d;
             }
             __syncthreads();
-            const T d = vec[1024];
+            const T d = vec[GENERIC_MAX_KP];
             for (int i = j + 1 + tid; i < kp; i += 256) G[tri_(i, j)] /= d;
             __syncthreads();
             const int m = kp - j - 1;

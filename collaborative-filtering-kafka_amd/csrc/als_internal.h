@@ -74,14 +74,7 @@ struct SqErrArgs {
     int64_t chunk_stride;
 };
 
-// Launch geometry of the generic path for (precision, kp): LDS or slab Gram, staged rows per batch, dynamic LDS.
-struct GenericPlan {
-    bool g_in_lds;
-    int batch;
-    int64_t lds_bytes;
-    int64_t slab_elems;   // elements per workgroup slab of SolveArgs::partials (0 when the Gram is in LDS)
-};
-GenericPlan generic_plan(int precision, int kp);
+// The generic path (als_generic.h) at the geometry of generic_plan(precision, kp) (als_plan.h).
 hipError_t launch_generic(int precision, int kp, const SolveArgs& a, hipStream_t s);
 
 // Launch helpers (defined in als_kernels.hip). Return hipSuccess or the launch error.

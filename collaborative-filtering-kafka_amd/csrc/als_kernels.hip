@@ -772,28 +772,6 @@ hipError_t launch_solve(int precision, int kp, Path path, const SolveArgs& a, hi
     return hipErrorInvalidValue;
 }
 
-GenericPlan generic_plan(int precision, int kp) {
-    GenericPlan p{};
-    const int64_t elem = precision == 0 ? 4 : 8;
-    const int64_t ntri = (int64_t)kp * (kp + 1) / 2;
-    const int64_t tri_b = ((ntri + 1) & ~(int64_t)1) * elem;
-    // LDS minus the kernel's static vectors (RHS / solution; fp64: the refinement's residual and batch residuals)
-    const int64_t avail = 160 * 1024 - 1025 * elem - (precision == 0 ? 2 * 4 : (1024 + 64) * 8);
-    const int64_t row_b = (int64_t)kp * elem;
-    if (tri_b + 8 * row_b <= avail) {
-        p.g_in_lds = true;
-        p.batch = (int)std::min<int64_t>(64, (avail - tri_b) / row_b);
-        p.lds_bytes = tri_b + p.batch * row_b;
-        p.slab_elems = 0;
-    } else {
-        p.g_in_lds = false;
-        p.batch = (int)std::max<int64_t>(1, std::min<int64_t>(64, (64 * 1024) / row_b));
-        p.lds_bytes = p.batch * row_b;
-        p.slab_elems = ntri + 1;
-    }
-    return p;
-}
-
 template <class T, bool L>
 hipError_t launch_generic_t(const GenericPlan& p, int kp, const SolveArgs& a, hipStream_t s) {
     hipError_t e = ensure_dyn_lds((const void*)als_solve_generic<T, L>, (int)p.lds_bytes);
@@ -808,7 +786,7 @@ hipError_t launch_generic_t(const GenericPlan& p, int kp, const SolveArgs& a, hi
 
 hipError_t launch_generic(int precision, int kp, const SolveArgs& a, hipStream_t s) {
     if (a.n_tasks <= 0) return hipSuccess;
-    if (kp > 1024 || kp % 16) return hipErrorInvalidValue;
+    if (kp > GENERIC_MAX_KP || kp % 16) return hipErrorInvalidValue;
     const GenericPlan p = generic_plan(precision, kp);
     if (precision == 0)
         return p.g_in_lds ? launch_generic_t<float, true>(p, kp, a, s) : launch_generic_t<float, false>(p, kp, a, s);

@@ -342,6 +342,30 @@ void partition_by_chunk(const std::vector<Task>& in, int n_chunks, const int64_t
     }
 }
 
+// The Gram stays in LDS while the packed triangle and GENERIC_MIN_LDS_BATCH staged rows fit beside the kernel's static
+// vectors; then the batch is whatever still fits, at most GENERIC_MAX_BATCH. Beyond that the triangle goes to a
+// per-workgroup global slab and the staged rows get GENERIC_SLAB_STAGE_BYTES.
+GenericPlan generic_plan(int precision, int kp) {
+    GenericPlan p{};
+    const bool f64 = precision != 0;
+    const int64_t elem = f64 ? 8 : 4;
+    const int64_t tri_b = generic_tri_elems(kp) * elem;
+    const int64_t avail = GENERIC_LDS_LIMIT - generic_static_lds_bytes(f64);
+    const int64_t row_b = (int64_t)kp * elem;
+    if (tri_b + GENERIC_MIN_LDS_BATCH * row_b <= avail) {
+        p.g_in_lds = true;
+        p.batch = (int)std::min<int64_t>(GENERIC_MAX_BATCH, (avail - tri_b) / row_b);
+        p.lds_bytes = tri_b + p.batch * row_b;
+        p.slab_elems = 0;
+    } else {
+        p.g_in_lds = false;
+        p.batch = (int)std::max<int64_t>(1, std::min<int64_t>(GENERIC_MAX_BATCH, GENERIC_SLAB_STAGE_BYTES / row_b));
+        p.lds_bytes = p.batch * row_b;
+        p.slab_elems = (int64_t)kp * (kp + 1) / 2 + 1;
+    }
+    return p;
+}
+
 RecommendPlan recommend_plan(int64_t n_users, int64_t n_cand, int top_n, int kp, int cu_count) {
     (void)kp;
     RecommendPlan p;

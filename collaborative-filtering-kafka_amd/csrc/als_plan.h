@@ -113,6 +113,39 @@ BlockPlan plan_build(const PlanKnobs& knobs, const BlockShape& shape, const Bloc
 void partition_by_chunk(const std::vector<Task>& in, int n_chunks, const int64_t* row_bounds, std::vector<Task>& out,
                         std::vector<int32_t>& off);
 
+// ---- the any-k path (als_generic.h) ---------------------------------------------------------------------------------
+// One 256-thread workgroup per row. Its static LDS is three vectors of the engine's element type: the RHS / solution of
+// GENERIC_MAX_KP features plus the pivot, and (fp64 only, else one element each) the refinement's residual and the
+// per-entry residuals of a batch of at most GENERIC_MAX_BATCH staged rows. The kernel sizes them with the functions
+// below and the plan budgets the dynamic LDS (packed triangle + staged rows) against what they leave, so neither can
+// change without the other.
+constexpr int GENERIC_MAX_KP = 1024;
+constexpr int GENERIC_MAX_BATCH = 64;
+constexpr int GENERIC_MIN_LDS_BATCH = 8;           // the Gram stays in LDS only while this many rows still fit beside it
+constexpr int64_t GENERIC_SLAB_STAGE_BYTES = 64 * 1024;   // staged rows of the slab variant
+constexpr int64_t GENERIC_LDS_LIMIT = 160 * 1024;  // LDS of one gfx950 compute unit
+constexpr int64_t GENERIC_LDS_ALIGN = 16;          // the dynamic region is 16-byte aligned: the statics round up to it
+CFK_HOST_DEVICE constexpr int generic_vec_elems() { return GENERIC_MAX_KP + 1; }
+CFK_HOST_DEVICE constexpr int generic_res_elems(bool f64) { return f64 ? GENERIC_MAX_KP : 1; }
+CFK_HOST_DEVICE constexpr int generic_tb_elems(bool f64) { return f64 ? GENERIC_MAX_BATCH : 1; }
+// Static LDS of als_solve_generic, alignment padding included: 4112 bytes in fp32, 16912 in fp64.
+CFK_HOST_DEVICE constexpr int64_t generic_static_lds_bytes(bool f64) {
+    return ((generic_vec_elems() + generic_res_elems(f64) + generic_tb_elems(f64)) * (int64_t)(f64 ? 8 : 4) +
+            GENERIC_LDS_ALIGN - 1) / GENERIC_LDS_ALIGN * GENERIC_LDS_ALIGN;
+}
+// Elements of the packed lower triangle of a kp x kp Gram, rounded up to an even count: the staged rows follow it.
+CFK_HOST_DEVICE constexpr int64_t generic_tri_elems(int kp) { return (((int64_t)kp * (kp + 1) / 2) + 1) & ~(int64_t)1; }
+
+// Launch geometry of the generic path for (precision, kp): LDS or slab Gram, staged rows per batch, dynamic LDS.
+struct GenericPlan {
+    bool g_in_lds;
+    int batch;
+    int64_t lds_bytes;
+    int64_t slab_elems;   // elements per workgroup slab of SolveArgs::partials (0 when the Gram is in LDS)
+};
+// precision: 0 fp32, 1 fp64; kp: the padded row stride, a multiple of 16 up to GENERIC_MAX_KP.
+GenericPlan generic_plan(int precision, int kp);
+
 // ---- top-N recommendation (als_recommend.hip) ----------------------------------------------------------------------
 // A 256-thread workgroup owns REC_USER_TILE query users and sweeps the REC_CAND_TILE-candidate tiles of one candidate
 // segment, REC_FEAT_CHUNK features staged per pass (row pitch REC_PITCH floats: odd, so the 16 rows a wave reads in

@@ -1,6 +1,7 @@
 // plan_check -- builds the work plan (csrc/als_plan.h) of small synthetic blocks on the CPU, checks the plan's
 // invariants from the plan alone and prints one JSON line per case: the layout, the counts, one boolean per invariant
-// and an FNV-1a digest of every output array (tests/golden/plan_digests.json pins the digests).
+// and an FNV-1a digest of every output array (tests/golden/plan_digests.json pins the digests). One more line holds the
+// launch geometry of the any-k path (generic_plan) for every padded stride, checked and digested the same way.
 // tests/test_plan_host.py compiles this file with als_plan.cpp under -fsanitize=address,undefined and runs it.
 #include <algorithm>
 #include <cstdint>
@@ -492,9 +493,52 @@ std::vector<Case> cases() {
     return v;
 }
 
+// The launch geometry of the any-k path (generic_plan) for every padded stride 16, 32, ..., 1024 in both precisions:
+// one row [precision, kp, g_in_lds, batch, lds_bytes, slab_elems] each, the invariants the kernel relies on, and a
+// digest of all 128 plans.
+void run_generic_plan() {
+    Fnv f;
+    Checks ck;
+    bool batch_ok = true, lds_ok = true, tri_ok = true, mono_ok = true, slab_ok = true, stage_ok = true;
+    printf("{\"case\": \"generic_launch_plan\", \"rows\": [");
+    for (int precision = 0; precision < 2; ++precision) {
+        const bool f64 = precision != 0;
+        const int64_t elem = f64 ? 8 : 4;
+        bool on_slab = false;
+        for (int kp = 16; kp <= GENERIC_MAX_KP; kp += 16) {
+            const GenericPlan p = generic_plan(precision, kp);
+            const int64_t ntri = (int64_t)kp * (kp + 1) / 2;
+            printf("%s[%d, %d, %d, %d, %lld, %lld]", precision || kp > 16 ? ", " : "", precision, kp, (int)p.g_in_lds,
+                   p.batch, (long long)p.lds_bytes, (long long)p.slab_elems);
+            f.i64(precision), f.i64(kp), f.i64(p.g_in_lds), f.i64(p.batch), f.i64(p.lds_bytes), f.i64(p.slab_elems);
+            batch_ok &= 1 <= p.batch && p.batch <= GENERIC_MAX_BATCH;
+            lds_ok &= p.lds_bytes + generic_static_lds_bytes(f64) <= GENERIC_LDS_LIMIT;
+            // the staged rows start at the triangle's even-rounded end (16-byte aligned in fp64, 8-byte in fp32)
+            const int64_t off = p.g_in_lds ? generic_tri_elems(kp) : 0;
+            tri_ok &= off % 2 == 0 && off >= (p.g_in_lds ? ntri : 0) && off <= ntri + 1;
+            stage_ok &= p.lds_bytes == (off + (int64_t)p.batch * kp) * elem;
+            mono_ok &= !(on_slab && p.g_in_lds);
+            on_slab |= !p.g_in_lds;
+            slab_ok &= p.slab_elems == (p.g_in_lds ? 0 : ntri + 1);
+        }
+        mono_ok &= on_slab;   // kp = 1024 cannot hold its triangle in LDS in either precision
+    }
+    ck.add("batch_1_to_64", batch_ok);
+    ck.add("static_plus_dynamic_lds_within_160k", lds_ok);
+    ck.add("triangle_offset_even", tri_ok);
+    ck.add("lds_bytes_are_triangle_plus_batch", stage_ok);
+    ck.add("slab_once_then_always", mono_ok);
+    ck.add("slab_elems_triangle_plus_one_or_zero", slab_ok);
+    ck.add("static_lds_4112_and_16912", generic_static_lds_bytes(false) == 4112 && generic_static_lds_bytes(true) == 16912);
+    printf("], \"invariants\": {");
+    for (size_t i = 0; i < ck.v.size(); ++i) printf("%s\"%s\": %s", i ? ", " : "", ck.v[i].first, ck.v[i].second ? "true" : "false");
+    printf("}, \"digest\": \"%016llx\"}\n", (unsigned long long)f.h);
+}
+
 }  // namespace
 
 int main() {
     for (const Case& c : cases()) run(c);
+    run_generic_plan();
     return 0;
 }

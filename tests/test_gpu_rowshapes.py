@@ -26,9 +26,7 @@ Over all fp32 cases of this module the largest per-row error was 2.0e-06 (k = 13
 1.4e-06 on the VALU Gram at k = 10, 1.3e-06 with ALS_GRAM=f32 or ALS_DUAL=0), over the fp64 cases 1.3e-14: the 1e-4 and
 1e-8 bounds have 50x and more to spare, and the nearest one-entry mutant is >= 1.5e-3 away.
 """
-import contextlib
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -39,34 +37,14 @@ import rowshapes as rs
 pytestmark = pytest.mark.gpu
 
 LAM = 0.05
-# every knob of the product library that selects a plan or a code path: cleared while an engine is created, so a case
-# runs exactly the knobs it names
-KNOBS = ("ALS_CHUNK", "ALS_INTERLEAVE", "ALS_XCD_RANGES", "ALS_PRESPLIT", "ALS_GRAM", "ALS_DUAL", "ALS_DUAL_SIDE",
-         "ALS_FORCE_VALU", "ALS_REFINE_MIN_PIVOT")
+KNOBS = rs.KNOBS      # the knobs a case may name; rs.knobs clears the rest while its engine is created
+_knobs = rs.knobs
 
 
 @pytest.fixture(autouse=True)
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-@contextlib.contextmanager
-def _knobs(env):
-    """The engine reads its knobs once, when it is created: set them for that moment only."""
-    assert set(env) <= set(KNOBS), env
-    saved = {v: os.environ.get(v) for v in KNOBS}
-    for v in KNOBS:
-        os.environ.pop(v, None)
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for v, old in saved.items():
-            if old is None:
-                os.environ.pop(v, None)
-            else:
-                os.environ[v] = old
 
 
 @functools.lru_cache(maxsize=None)

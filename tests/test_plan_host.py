@@ -14,6 +14,7 @@ import subprocess
 
 import pytest
 
+import rowshapes as rs
 from conftest import GOLDEN, ROOT
 
 CSRC = os.path.join(ROOT, "collaborative-filtering-kafka_amd", "csrc")
@@ -163,6 +164,31 @@ def test_split_and_entry_space_counts(plan_cases):
     assert plan_cases["generic_k130"]["n_reduce"] == 0 and max(plan_cases["generic_k130"]["deg"]) == 100000
     # the rows the cases are about are there
     assert 41 in plan_cases["split_kp64_k40"]["deg"] and 80 in plan_cases["split_kp128_k70"]["deg"]
+
+
+def test_generic_launch_plan(plan_cases):
+    """generic_plan (the any-k path's launch geometry) for kp = 16, 32, ..., 1024 in both precisions: the invariants
+    plan_check computes, the switch points from the LDS to the slab Gram with their part-full batches, the tightest
+    launch, and the Python restatement (rowshapes.generic_plan, which the GPU tests use to say which variant a case
+    runs) equal to the C++ on all 128 pairs."""
+    c = plan_cases["generic_launch_plan"]
+    assert len(c["invariants"]) == 7 and all(c["invariants"].values()), c["invariants"]
+    rows = {(("f32", "f64")[r[0]], r[1]): rs.GenericPlan(bool(r[2]), r[3], r[4], r[5]) for r in c["rows"]}
+    assert sorted(rows) == [(p, kp) for p in ("f32", "f64") for kp in range(16, 1025, 16)] and len(rows) == 128
+    for (precision, kp), got in rows.items():
+        assert rs.generic_plan(precision, kp) == got, (precision, kp, got)
+    # last kp with the Gram in LDS, its batch, first slab kp
+    for precision, last, batch in (("f32", 272, 10), ("f64", 176, 15)):
+        assert [kp for (p, kp), g in rows.items() if p == precision and g.g_in_lds][-1] == last
+        assert rows[precision, last].batch == batch and not rows[precision, last + 16].g_in_lds
+    # the launch geometry test_gpu_anyk.py runs on
+    want = {("f32", 144): (True, 64), ("f32", 272): (True, 10), ("f32", 288): (False, 56), ("f32", 512): (False, 32),
+            ("f32", 1024): (False, 16), ("f64", 80): (True, 64), ("f64", 144): (True, 55), ("f64", 176): (True, 15),
+            ("f64", 192): (False, 42), ("f64", 1024): (False, 8)}
+    assert {key: (rows[key].g_in_lds, rows[key].batch) for key in want} == want
+    # the tightest launch: fp64 kp = 144, 48 bytes under the 160 KiB of a compute unit
+    total = {key: g.lds_bytes + rs.GENERIC_STATIC_LDS[key[0]] for key, g in rows.items()}
+    assert max(total, key=total.get) == ("f64", 144) and total["f64", 144] == 163_840 - 48
 
 
 def test_digests_match_golden(plan_cases):

@@ -6,6 +6,10 @@ dropped, last rating off by 1) is rejected on every row of >= 2 entries, and eve
 away from its nearest mutant -- a condition on the inputs (signed unit-norm factors), not a measurement of a kernel.
 The contrast case records why the inputs changed: on uniform [0, 1) factors the global envelope the older tests use
 accepts a row that lost its last entry.
+
+The same two facts for the any-k ladders of test_gpu_anyk.py (k = 65 .. 1024, and its grid-stride blocks): there the
+reference's fp32 error on the one-rating row grows with k and passes 2e-5 at k = 1010 and 1024, so those two cases get
+the bound the rule in rowshapes.py gives them (5 x the reference's worst row); the nearest mutant stays >= 9e-3 away.
 """
 import numpy as np
 import pytest
@@ -81,6 +85,61 @@ def test_comparator_accepts_the_reference_and_rejects_every_mutant(ladder, k, la
     worst = int(np.argmin(np.where(two, nearest, np.inf)))
     print(f"k={k} lam={lam}: nearest mutant {nearest[worst]:.2e} away (row of {degs[worst]} entries)")
     assert nearest[worst] >= rs.MARGIN * rs.BOUND["f32"], (k, lam, degs[worst], nearest[worst])
+
+
+ANYK = [(k, 0) for k in sorted({c[1] for c in rs.ANYK_CASES})] + [(k, rows) for _, k, rows in rs.ANYK_STRIDE_CASES]
+
+
+def test_anyk_ladders_are_what_they_say():
+    small, wide, stride = rs.anyk_ladder(129), rs.anyk_ladder(1010), rs.anyk_ladder(273, 1100)
+    assert sorted(small.degs.tolist()) == sorted((1, 2, 3, 9, 10, 11, 15, 16, 31, 32, 33, 55, 56, 64, 65, 97, 130, 257,
+                                                  330, 0, 0)) and small.n_opp == 512
+    assert wide.degs.tolist() == small.degs.tolist() + [1100] and wide.n_opp == 1280
+    assert np.array_equal(rs.anyk_ladder(1024).blk["col"], wide.blk["col"])
+    assert np.array_equal(rs.anyk_ladder(500).blk["col"], small.blk["col"])
+    assert stride.degs.tolist() == [1 + i % 40 for i in range(1100)] and stride.n_opp == 512
+    # every batch of the launch plans the cases run on has a row one short of it, at it and (<= 64) one over it or
+    # a row that fills several: 8, 10, 15, 16, 55, 64 staged rows, and the 32-entry block
+    for b in (10, 15, 16, 32, 55, 64):
+        assert {b, b + 1} <= set(small.degs.tolist()) or {b - 1, b} <= set(small.degs.tolist()), b
+    for precision, k, kp, in_lds, batch in rs.ANYK_CASES:
+        assert kp == -(-k // 16) * 16 and k > (64 if precision == "f64" else 128)
+        assert rs.generic_plan(precision, kp)[:2] == (in_lds, batch), (precision, k)
+        assert rs.anyk_ladder(k).degs.max() > k or k < 1010
+
+
+@pytest.mark.parametrize("k,rows", ANYK, ids=lambda v: str(v))
+def test_anyk_reference_margin_and_mutant_margin(k, rows):
+    """The yardstick of test_gpu_anyk.py, settled with the oracle alone: on the any-k ladders the reference's own fp32
+    arithmetic stays at or below bound / MARGIN on every row, and every one-entry mutant is at least MARGIN x bound
+    away -- at the bound rowshapes.anyk_bound gives that k (1e-4, or 5 x the reference's worst row where that is
+    more: k = 1010 and 1024, whose recorded figures are re-measured here)."""
+    lad, F, ref64, ref32 = rs.anyk_inputs(k, rows)
+    degs = lad.degs
+    bound = rs.anyk_bound("f32", k)
+    rel32 = rs.row_errors(ref32, ref64)
+    worst = float(rel32[degs > 0].max())
+    print(f"k={k} rows={len(degs)}: reference fp32 per-row max {worst:.3e} (row of {degs[rel32.argmax()]} entries), "
+          f"bound {bound:.3e}")
+    if k in rs.ANYK_REF32_WORST:     # the recorded figure is this measurement, rounded up in its third digit
+        assert rs.BOUND["f32"] / rs.MARGIN < worst <= rs.ANYK_REF32_WORST[k] <= 1.01 * worst
+        assert bound == rs.MARGIN * rs.ANYK_REF32_WORST[k]
+    else:
+        assert bound == rs.BOUND["f32"]
+    assert worst <= bound / rs.MARGIN
+    rs.check_rows(ref32, ref64, ref32, degs, "f32", bound=bound)
+    rs.check_rows(ref64, ref64, None, degs, "f64")
+    two = degs >= 2
+    nearest = np.full(len(degs), np.inf)
+    for name, mside in rs.mutants(lad.side).items():
+        mut = rs.oracle.update_side(mside, F, rs.ANYK_LAM, "f64")
+        for precision in ("f32", "f64"):
+            bad = rs.rejected_rows(mut, ref64, degs, precision, rs.anyk_bound(precision, k))
+            assert bad[two].all() and not bad[~two].any(), (name, precision, degs[two & ~bad][:8])
+        nearest = np.minimum(nearest, rs.row_errors(mut, ref64))
+    i = int(np.argmin(np.where(two, nearest, np.inf)))
+    print(f"k={k}: nearest mutant {nearest[i]:.2e} away (row of {degs[i]} entries)")
+    assert nearest[i] >= rs.MARGIN * bound, (k, degs[i], nearest[i])
 
 
 def test_comparator_rejects_other_damage(ladder):
