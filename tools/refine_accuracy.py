@@ -9,6 +9,11 @@ parity tests bound by 2 and 3.
   CFK_ALS_LIB=collaborative-filtering-kafka_amd/build_debug/libcfk_als.so python tools/refine_accuracy.py [thresholds...]
 
 Thresholds below the validated 0.45 gate need the debug build (`make debug`): the product library clamps them.
+
+This tool is a hand-run experiment on uniform [0, 1) factors at lambda = 0.05. The standing check of the gate and of the
+refinement step -- rows on both sides of 0.45 and next to it, every residual implementation, per-row bounds per pivot
+bucket, the unrefined solve for comparison -- is tests/test_gpu_conditioning.py (inputs: tests/conditioning.py, their
+conditions proved in tests/test_conditioning_host.py).
 """
 import json
 import os
