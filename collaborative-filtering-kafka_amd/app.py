@@ -66,6 +66,68 @@ def seen_exclusions(ds: Dataset, world: int, rank: int, movie_rows) -> tuple[np.
     return rows, excl_ptr, pos[keep].astype(np.int32)
 
 
+def heldout_queries(ds: Dataset, movie_ids, user_ids, world: int, rank: int, movie_rows):
+    """What ALSEngine.rank_targets needs to evaluate held-out (movie id, user id) pairs. For rank `rank`'s users in
+    shard_user_rows order (ascending raw id): (tgt_ptr, tgt_idx, entry, seen, n_unknown, n_seen).
+    tgt_idx[tgt_ptr[i]:tgt_ptr[i + 1]] = the positions in `movie_rows` (movie factor rows = slots, any subset, repeats
+    allowed: a slot listed several times is taken at its first position) of user i's held-out movies, in input order;
+    entry[t] = the index of the input pair behind target t. Only pairs of this rank's shard (user id % world == rank)
+    are looked at. n_unknown of them are skipped: the user or the movie is not in `ds`, or the movie is not in
+    `movie_rows`. seen[t] marks the n_seen targets that are also training ratings of that user: they keep their score
+    but a caller that excludes seen movies leaves them out of the ranks. Pure host code."""
+    mid = np.ascontiguousarray(movie_ids, np.int64)
+    uid = np.ascontiguousarray(user_ids, np.int64)
+    if mid.shape != uid.shape or mid.ndim != 1:
+        raise ValueError("movie_ids and user_ids must be one-dimensional and of equal length")
+    blk = ds.shard_block(SIDE_USER, world, rank)
+    mine = np.asarray(blk["row_ids"], np.int64)               # ascending raw id = local-row order
+    all_movies = ds.ids(SIDE_MOVIE)
+    slot_of = ds.slots(SIDE_MOVIE, world)
+    mr = np.ascontiguousarray(movie_rows, np.int64)
+    order = np.argsort(mr, kind="stable")                     # stable: the first position of a repeated slot first
+    by_slot = mr[order]
+    own = np.nonzero(uid % world == rank)[0] if world > 1 else np.arange(len(uid), dtype=np.int64)
+    u, m = uid[own], mid[own]
+    ui = np.minimum(np.searchsorted(mine, u), max(len(mine) - 1, 0))
+    mi = np.minimum(np.searchsorted(all_movies, m), max(len(all_movies) - 1, 0))
+    known = (mine[ui] == u if len(mine) else np.zeros(len(u), bool)) & \
+        (all_movies[mi] == m if len(all_movies) else np.zeros(len(u), bool))
+    slot = slot_of[mi] if len(all_movies) else np.zeros(len(u), np.int64)
+    at = np.minimum(np.searchsorted(by_slot, slot, "left"), max(len(mr) - 1, 0))
+    known &= (by_slot[at] == slot) if len(mr) else False
+    pos = order[at] if len(mr) else np.zeros(len(u), np.int64)
+    own, ui, pos, slot = own[known], ui[known], pos[known], slot[known]
+    keep = np.argsort(ui, kind="stable")                      # by user, input order inside a user
+    own, ui, pos, slot = own[keep], ui[keep], pos[keep], slot[keep]
+    tgt_ptr = np.zeros(len(mine) + 1, np.int64)
+    np.cumsum(np.bincount(ui, minlength=len(mine)), out=tgt_ptr[1:])
+    # seen: (local row, movie slot) is an entry of this shard's user in-block
+    n_slots = int(slot_of.max()) + 1 if len(slot_of) else 1
+    rated = np.repeat(np.arange(len(mine), dtype=np.int64), np.diff(blk["row_ptr"])) * n_slots + blk["col"].astype(np.int64)
+    seen = np.isin(ui * n_slots + slot, rated)
+    return tgt_ptr, pos.astype(np.int32), own.astype(np.int64), seen, int(len(u) - len(own)), int(seen.sum())
+
+
+def ranking_metrics(rank, n_eligible, top_n: int) -> dict:
+    """Ranking quality from exact 0-based ranks (ALSEngine.rank_targets), pure numpy in float64: HR@N = mean(rank < N),
+    NDCG@N = mean(1 / log2(rank + 2) where rank < N, else 0), MRR = mean(1 / (rank + 1)), MPR = mean(rank /
+    max(1, n_eligible - 1)) with n_eligible per target = the candidates its user may be recommended (n_movies minus the
+    user's exclusions). Returns the means ("hr", "ndcg", "mrr", "mpr"; nan without targets), "n_ranked" and the sums
+    ("hr_sum", ...), which add across ranks."""
+    r = np.asarray(rank, np.float64)
+    ne = np.broadcast_to(np.asarray(n_eligible, np.float64), r.shape)
+    hit = r < top_n
+    sums = {"hr_sum": float(np.count_nonzero(hit)),
+            "ndcg_sum": float(np.sum(np.where(hit, 1.0 / np.log2(r + 2.0), 0.0))),
+            "mrr_sum": float(np.sum(1.0 / (r + 1.0))),
+            "mpr_sum": float(np.sum(r / np.maximum(1.0, ne - 1.0)))}
+    n = int(r.size)
+    out = {"n_ranked": n, **sums}
+    for key in ("hr", "ndcg", "mrr", "mpr"):
+        out[key] = sums[key + "_sum"] / n if n else float("nan")
+    return out
+
+
 class ALSApp:
     # a movie factor table above this is exchanged in chunks (N > 1): configs[4]'s 256 MB item table (all-gather ~1.7 ms
     # at G = 8), not the 9 MB k = 128 Netflix one -- its 4 chunk launches cost more in launch tails than the overlap of a
@@ -295,6 +357,36 @@ class ALSApp:
             user_ids = user_ids[user_ids % self.world == self.rank]
         out = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
         return user_ids, out.astype(np.int64), score
+
+    def evaluate(self, movie_ids, user_ids, ratings, top_n: int = 10, exclude_seen: bool = True,
+                 ranks: bool = True) -> dict:
+        """Held-out evaluation of the (movie id, user id, rating) triples that belong to this rank's users, from the
+        (gathered) factor replicas and against all movies in ascending id (ALSEngine.rank_targets: exact scores, exact
+        ranks under recommend()'s order). No collective: every rank answers for its own users and the sums add across
+        ranks. Returns the sums se, ae (errors (double)r - (double)score, summed in float64) and n over the scored
+        triples; n_unknown (user or movie not in the training data: skipped) and n_seen (also a training rating: scored,
+        but with exclude_seen left out of the ranks); n_ranked and hr_sum, ndcg_sum, mrr_sum, mpr_sum over the ranked
+        ones (ranking_metrics, n_eligible = the movies minus the user's seen ones); and the derived rmse, mae, hr, ndcg,
+        mrr, mpr (nan where nothing was counted). ranks=False: errors only, no candidate sweep."""
+        movie_rows = self.ds.slots(SIDE_MOVIE, self.world)       # ascending id -> factor row
+        user_rows, excl_ptr, excl_idx = seen_exclusions(self.ds, self.world, self.rank, movie_rows)
+        tgt_ptr, tgt_idx, entry, seen, n_unknown, n_seen = heldout_queries(self.ds, movie_ids, user_ids, self.world,
+                                                                           self.rank, movie_rows)
+        excl = (excl_ptr, excl_idx) if exclude_seen else None
+        score, rank = self.engine.rank_targets(user_rows, movie_rows, (tgt_ptr, tgt_idx), excl, ranks=ranks)
+        err = np.asarray(ratings, np.float64)[entry] - score.astype(np.float64)
+        out = {"top_n": int(top_n), "se": float(np.sum(err * err)), "ae": float(np.sum(np.abs(err))), "n": int(len(err)),
+               "n_unknown": n_unknown, "n_seen": n_seen}
+        if ranks:
+            counted = ~seen if exclude_seen else np.ones(len(seen), bool)
+            n_excl = np.diff(excl_ptr) if exclude_seen else np.zeros(len(user_rows), np.int64)
+            n_eligible = np.repeat(len(movie_rows) - n_excl, np.diff(tgt_ptr))
+            out.update(ranking_metrics(rank[counted], n_eligible[counted], top_n))
+        else:
+            out.update(ranking_metrics(np.zeros(0), np.zeros(0), top_n))
+        out["rmse"] = float(np.sqrt(out["se"] / out["n"])) if out["n"] else float("nan")
+        out["mae"] = out["ae"] / out["n"] if out["n"] else float("nan")
+        return out
 
     def sq_error(self):
         """Sum of squared errors over all observed ratings (all ranks) and the rating count."""

@@ -2,6 +2,7 @@
 //
 //   als_app NUM_PARTITIONS NUM_FEATURES LAMBDA NUM_ITERATIONS dataset NUM_MOVIES NUM_USERS
 //           [--precision f32|f64] [--seed S] [--gpus G] [--out DIR] [--top-n N] [--no-matrix]
+//           [--probe FILE] [--probe-top-n N]
 //
 // Same 7 positional arguments (README.md:35); the extras are optional trailing flags. The run follows the
 // reference topology (ALSApp.java:52-184) bulk-synchronously: ingest (NetflixDataFormatProducer), in-blocks
@@ -15,6 +16,9 @@
 // --top-n N (1..64) additionally writes <out>/recommendations_<timestamp>: per user, ascending id, its N best-scoring
 // movies not rated yet as lines "userId,movieId,score" (als_recommend: no dense matrix); --no-matrix skips the
 // prediction matrix and its CSV, which do not fit at full scale. Without them the output is the reference's.
+// --probe FILE evaluates held-out ratings (Netflix format, the training file's loader) after training and prints
+// "probe n=... unknown=... seen=... ranked=... rmse=... mae=... hr@N=... ndcg@N=... mrr=... mpr=..." (als_rank_targets:
+// exact scores and exact ranks against all movies the user has not rated; N = --probe-top-n, 1..64, default 10).
 // Deviations that turn reference hangs into errors: duplicate (user, movie) pairs, and NUM_MOVIES /
 // NUM_USERS not equal to the rated-entity counts (FeatureCollector.java:43 would never fire).
 #include <sys/stat.h>
@@ -91,7 +95,8 @@ int main(int argc, char** argv) {
     unsigned long long seed = 42;
     int gpus = 0;
     std::string outdir = "./predictions";
-    long long top_n = 0;
+    long long top_n = 0, probe_top_n = 10;
+    const char* probe = nullptr;
     bool matrix = true;
     for (int i = 8; i < argc; ++i) {
         std::string a = argv[i];
@@ -109,6 +114,13 @@ int main(int argc, char** argv) {
         } else if (a == "--top-n" && i + 1 < argc) {
             if (!parse_int(argv[++i], 1, 64, top_n)) {
                 fprintf(stderr, "als_app: --top-n 1..64\n");
+                return 1;
+            }
+        } else if (a == "--probe" && i + 1 < argc) {
+            probe = argv[++i];
+        } else if (a == "--probe-top-n" && i + 1 < argc) {
+            if (!parse_int(argv[++i], 1, 64, probe_top_n)) {
+                fprintf(stderr, "als_app: --probe-top-n 1..64\n");
                 return 1;
             }
         } else if (a == "--no-matrix") {
@@ -226,20 +238,23 @@ int main(int argc, char** argv) {
         if (als_write_prediction_matrix_csv(path.c_str(), pred.data(), nu, nm) != ALS_OK) return die("csv");
         printf("Prediction matrix: %s\n", path.c_str());
     }
-    if (top_n > 0) {
-        // Candidates = all movies in ascending id (ties go to the smaller id); excluded per user = the movies it rated:
-        // the unsharded user in-block lists them as dense movie indices, which are the candidate positions.
+    // Candidates = all movies in ascending id (ties go to the smaller id); excluded per user = the movies it rated:
+    // the unsharded user in-block lists them as dense movie indices, which are the candidate positions.
+    std::vector<int64_t> eptr, uid, mid;
+    std::vector<int32_t> eidx;
+    if (top_n > 0 || probe) {
         int64_t n_rows, row_off, bnnz, s1, ns1;
         if (als_dataset_shard_info(ds, ALS_SIDE_USER, 1, 0, &n_rows, &row_off, &bnnz, &s1, &ns1) != ALS_OK)
             return die("shard_info");
-        std::vector<int64_t> eptr(n_rows + 1), uid(nu), mid(nm);
-        std::vector<int32_t> eidx(bnnz);
+        eptr.resize(n_rows + 1), uid.resize(nu), mid.resize(nm), eidx.resize(bnnz);
         std::vector<int16_t> erat(bnnz);
         if (als_dataset_shard_block(ds, ALS_SIDE_USER, 1, 0, eptr.data(), eidx.data(), erat.data(), nullptr) != ALS_OK)
             return die("user in-blocks");
         for (int64_t u = 0; u < n_rows; ++u) std::sort(eidx.begin() + eptr[u], eidx.begin() + eptr[u + 1]);
         if (als_dataset_ids(ds, ALS_SIDE_USER, uid.data()) != ALS_OK || als_dataset_ids(ds, ALS_SIDE_MOVIE, mid.data()) != ALS_OK)
             return die("ids");
+    }
+    if (top_n > 0) {
         std::vector<int32_t> idx((size_t)nu * top_n);
         std::vector<float> score((size_t)nu * top_n);
         if (als_recommend(eng[0], urows.data(), nu, mrows.data(), nm, (int)top_n, eptr.data(), eidx.data(), idx.data(),
@@ -251,6 +266,73 @@ int main(int argc, char** argv) {
         if (als_write_recommendations_csv(path.c_str(), uid.data(), nu, (int)top_n, movie.data(), score.data()) != ALS_OK)
             return die("recommendations");
         printf("Recommendations: %s\n", path.c_str());
+    }
+    if (probe) {
+        // Held-out triples: the users in ascending id are the query users, a triple's target is its movie's position.
+        // Unknown ids are skipped; a triple that is also a training rating keeps its score and is left out of the ranks.
+        als_dataset* pds = nullptr;
+        if (als_dataset_load_netflix(probe, &pds) != ALS_OK) return die("probe");
+        int64_t pm, pu, pn;
+        als_dataset_counts(pds, &pm, &pu, &pn);
+        std::vector<int32_t> p_movie(pn), p_user(pn);
+        std::vector<int16_t> p_rat(pn);
+        if (als_dataset_ratings(pds, p_movie.data(), p_user.data(), p_rat.data()) != ALS_OK) return die("probe ratings");
+        als_dataset_destroy(pds);
+        std::vector<int64_t> tptr(nu + 1, 0);
+        std::vector<int64_t> t_user(pn, -1), t_pos(pn, -1);
+        int64_t n_unknown = 0;
+        for (int64_t i = 0; i < pn; ++i) {
+            const auto u = std::lower_bound(uid.begin(), uid.end(), (int64_t)p_user[i]);
+            const auto m = std::lower_bound(mid.begin(), mid.end(), (int64_t)p_movie[i]);
+            if (u == uid.end() || *u != p_user[i] || m == mid.end() || *m != p_movie[i]) {
+                ++n_unknown;
+                continue;
+            }
+            t_user[i] = u - uid.begin();
+            t_pos[i] = m - mid.begin();
+            ++tptr[t_user[i] + 1];
+        }
+        for (int64_t u = 0; u < nu; ++u) tptr[u + 1] += tptr[u];
+        const int64_t T = tptr[nu];
+        std::vector<int32_t> tidx(std::max<int64_t>(T, 1));
+        std::vector<int64_t> entry(T), fill(tptr.begin(), tptr.end() - 1);
+        for (int64_t i = 0; i < pn; ++i)   // input order inside every user
+            if (t_user[i] >= 0) {
+                const int64_t t = fill[t_user[i]]++;
+                tidx[t] = (int32_t)t_pos[i];
+                entry[t] = i;
+            }
+        std::vector<float> score(std::max<int64_t>(T, 1));
+        std::vector<int32_t> rank(std::max<int64_t>(T, 1));
+        if (als_rank_targets(eng[0], urows.data(), nu, mrows.data(), nm, tptr.data(), tidx.data(), eptr.data(), eidx.data(),
+                             score.data(), rank.data()) != ALS_OK)
+            return die("rank_targets");
+        double se = 0, ae = 0, hr = 0, ndcg = 0, mrr = 0, mpr = 0;
+        int64_t n_seen = 0, n_ranked = 0;
+        for (int64_t u = 0; u < nu; ++u) {
+            const double eligible = (double)(nm - (eptr[u + 1] - eptr[u]));
+            for (int64_t t = tptr[u]; t < tptr[u + 1]; ++t) {
+                const double err = (double)p_rat[entry[t]] - (double)score[t];
+                se += err * err;
+                ae += std::fabs(err);
+                if (std::binary_search(eidx.begin() + eptr[u], eidx.begin() + eptr[u + 1], tidx[t])) {
+                    ++n_seen;
+                    continue;
+                }
+                const double r = rank[t];
+                ++n_ranked;
+                if (r < (double)probe_top_n) {
+                    hr += 1;
+                    ndcg += 1.0 / std::log2(r + 2.0);
+                }
+                mrr += 1.0 / (r + 1.0);
+                mpr += r / std::max(1.0, eligible - 1.0);
+            }
+        }
+        const double dn = T ? (double)T : NAN, dr = n_ranked ? (double)n_ranked : NAN;
+        printf("probe n=%lld unknown=%lld seen=%lld ranked=%lld rmse=%.6f mae=%.6f hr@%lld=%.6f ndcg@%lld=%.6f mrr=%.6f "
+               "mpr=%.6f\n", (long long)T, (long long)n_unknown, (long long)n_seen, (long long)n_ranked, std::sqrt(se / dn),
+               ae / dn, probe_top_n, hr / dr, probe_top_n, ndcg / dr, mrr / dr, mpr / dr);
     }
     for (auto* e : eng) als_engine_destroy(e);
     als_dataset_destroy(ds);

@@ -157,7 +157,8 @@ struct als_engine {
                                     //   opposite table was last split at
     int prep_set = 0;               // the set of the last preparation: SolveArgs::amax of the half it served
     cfk::DeviceBuf<char> d_rec;     // als_recommend's own grow-only workspace (rows, exclusion CSR, partial and final
-                                    //   lists): never d_partials / d_split / d_prep, which a half in progress owns
+                                    //   lists): never d_partials / d_split / d_prep, which a half in progress owns.
+                                    //   als_rank_targets uses it too: both calls are synchronous
     cfk::PinnedBuf h_stage;         // pinned staging of als_write_factors / als_read_factors (copy kernels)
     cfk::DeviceBuf<uint32_t> d_integrity;   // cfk::INTEGRITY_WORDS: partial slots that failed their check
     int cu_count = 0;               // compute units of the device: the range guard's fallback grid

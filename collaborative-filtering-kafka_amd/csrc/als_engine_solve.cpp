@@ -1,5 +1,5 @@
 // als_engine_solve.cpp -- what runs on the resident factors: factor buffers and their I/O, the half-iteration launch,
-// squared error, predict and recommend. The steady-state half (launch_half) allocates nothing and creates no stream
+// squared error, predict, recommend and held-out ranks. The steady-state half (launch_half) allocates nothing and creates no stream
 // or event: the side stream and its two events are made by the first half that needs them, timing events come from
 // the engine's pool.
 #include "als_engine_impl.h"
@@ -32,6 +32,25 @@ int check_query_rows(const als_engine* e, const int64_t* user_rows, int64_t n_us
         if (user_rows[i] < 0 || user_rows[i] >= nu) return fail(ALS_ERR_INVALID_ARGUMENT, "user row out of range");
     for (int64_t i = 0; i < n_movies; ++i)
         if (movie_rows[i] < 0 || movie_rows[i] >= nm) return fail(ALS_ERR_INVALID_ARGUMENT, "movie row out of range");
+    return ALS_OK;
+}
+
+// The exclusion CSR of als_recommend / als_rank_targets (`fn` names the call in the message), O(nnz): ranges in order,
+// positions strictly ascending per user and inside the candidate set.
+int check_exclusions(const char* fn, const int64_t* excl_ptr, const int32_t* excl_idx, int64_t n_users, int64_t n_movies) {
+    if (excl_ptr[0] < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: excl_ptr[0] is negative", fn);
+    for (int64_t u = 0; u < n_users; ++u) {
+        const int64_t lo = excl_ptr[u], hi = excl_ptr[u + 1];
+        if (hi < lo) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: excl_ptr decreases at user %lld", fn, (long long)u);
+        for (int64_t x = lo; x < hi; ++x) {
+            if (excl_idx[x] < 0 || excl_idx[x] >= n_movies)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: excluded position %d of user %lld is outside [0, %lld)", fn,
+                            (int)excl_idx[x], (long long)u, (long long)n_movies);
+            if (x > lo && excl_idx[x] <= excl_idx[x - 1])
+                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: excluded positions of user %lld are not strictly ascending", fn,
+                            (long long)u);
+        }
+    }
     return ALS_OK;
 }
 
@@ -347,21 +366,9 @@ int als_recommend(als_engine* e, const int64_t* user_rows, int64_t n_users, cons
     if (!user_rows || !movie_rows || !host_idx || !host_score) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
     if (int r = check_query_rows(e, user_rows, n_users, movie_rows, n_movies)) return r;
     int64_t ex0 = 0, ex_nnz = 0;
-    if (excl_ptr) {   // O(nnz): ranges in order, positions strictly ascending per user and inside the candidate set
+    if (excl_ptr) {
+        if (int r = check_exclusions("als_recommend", excl_ptr, excl_idx, n_users, n_movies)) return r;
         ex0 = excl_ptr[0];
-        if (ex0 < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: excl_ptr[0] is negative");
-        for (int64_t u = 0; u < n_users; ++u) {
-            const int64_t lo = excl_ptr[u], hi = excl_ptr[u + 1];
-            if (hi < lo) return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: excl_ptr decreases at user %lld", (long long)u);
-            for (int64_t x = lo; x < hi; ++x) {
-                if (excl_idx[x] < 0 || excl_idx[x] >= n_movies)
-                    return fail(ALS_ERR_INVALID_ARGUMENT, "als_recommend: excluded position %d of user %lld is outside [0, %lld)",
-                                (int)excl_idx[x], (long long)u, (long long)n_movies);
-                if (x > lo && excl_idx[x] <= excl_idx[x - 1])
-                    return fail(ALS_ERR_INVALID_ARGUMENT,
-                                "als_recommend: excluded positions of user %lld are not strictly ascending", (long long)u);
-            }
-        }
         ex_nnz = excl_ptr[n_users] - ex0;
     }
     const cfk::RecommendPlan p = cfk::recommend_plan(n_users, n_movies, top_n, e->kp, e->cu_count);
@@ -411,6 +418,114 @@ int als_recommend(als_engine* e, const int64_t* user_rows, int64_t n_users, cons
     const hipError_t st2 = hipStreamSynchronize(e->stream);
     if (st == hipSuccess) st = st2;
     if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_recommend: %s", hipGetErrorString(st));
+    return sync_checked(e);
+}
+
+int als_rank_plan(const als_engine* e, int64_t n_targets, int64_t n_movies, int64_t info[4]) {
+    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (n_targets < 0 || n_movies < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "negative counts");
+    const cfk::RankPlan p = cfk::rank_plan(n_targets, n_movies, e->kp, e->cu_count);
+    info[0] = p.tgt_tile;
+    info[1] = p.segments;
+    info[2] = p.seg_len;
+    info[3] = p.lds_bytes;
+    return ALS_OK;
+}
+
+int als_rank_targets(als_engine* e, const int64_t* user_rows, int64_t n_users, const int64_t* movie_rows, int64_t n_movies,
+                     const int64_t* tgt_ptr, const int32_t* tgt_idx, const int64_t* excl_ptr, const int32_t* excl_idx,
+                     float* host_score, int32_t* host_rank) {
+    if (int r = check_engine(e)) return r;
+    if (n_users < 0 || n_movies < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "negative counts");
+    if (!tgt_ptr || !tgt_idx) return fail(ALS_ERR_INVALID_ARGUMENT, "als_rank_targets: tgt_ptr and tgt_idx must both be given");
+    if ((excl_ptr == nullptr) != (excl_idx == nullptr))
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_rank_targets: excl_ptr and excl_idx must both be given or both be NULL");
+    if (n_movies > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "als_rank_targets: n_movies must be below 2^31");
+    if (n_users > INT32_MAX) return fail(ALS_ERR_UNSUPPORTED, "als_rank_targets: at most 2^31 - 1 query users per call");
+    const Factors& U = e->fac[ALS_SIDE_USER];
+    const Factors& M = e->fac[ALS_SIDE_MOVIE];
+    if (!U.ptr || !M.ptr) return fail(ALS_ERR_STATE, "als_rank_targets: factor matrices not allocated/bound");
+    if (n_users == 0) return ALS_OK;
+    const int64_t t0 = tgt_ptr[0];
+    if (t0 < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_rank_targets: tgt_ptr[0] is negative");
+    for (int64_t u = 0; u < n_users; ++u)
+        if (tgt_ptr[u + 1] < tgt_ptr[u])
+            return fail(ALS_ERR_INVALID_ARGUMENT, "als_rank_targets: tgt_ptr decreases at user %lld", (long long)u);
+    const int64_t T = tgt_ptr[n_users] - t0;
+    if (T > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "als_rank_targets: the number of targets must be below 2^31");
+    if (T == 0 || (host_rank && n_movies == 0)) return ALS_OK;
+    if (!user_rows || !movie_rows || !host_score) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (int r = check_query_rows(e, user_rows, n_users, movie_rows, n_movies)) return r;
+    // per target entry: its user's factor row and its query-user index (the exclusion range)
+    std::vector<int64_t> trow((size_t)T);
+    std::vector<int32_t> tuser((size_t)T);
+    for (int64_t u = 0; u < n_users; ++u)
+        for (int64_t x = tgt_ptr[u]; x < tgt_ptr[u + 1]; ++x) {
+            if (tgt_idx[x] < 0 || tgt_idx[x] >= n_movies)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "als_rank_targets: target position %d of user %lld is outside [0, %lld)",
+                            (int)tgt_idx[x], (long long)u, (long long)n_movies);
+            trow[(size_t)(x - t0)] = user_rows[u];
+            tuser[(size_t)(x - t0)] = (int32_t)u;
+        }
+    const bool with_excl = excl_ptr && host_rank;   // the scores do not depend on the exclusions
+    int64_t ex0 = 0, ex_nnz = 0;
+    if (excl_ptr) {
+        if (int r = check_exclusions("als_rank_targets", excl_ptr, excl_idx, n_users, n_movies)) return r;
+        ex0 = excl_ptr[0];
+        ex_nnz = excl_ptr[n_users] - ex0;
+    }
+    const cfk::RankPlan p = cfk::rank_plan(T, n_movies, e->kp, e->cu_count);
+    if (p.lds_bytes > cfk::RANK_LDS_LIMIT) return fail(ALS_ERR_UNSUPPORTED, "als_rank_targets: launch plan exceeds the LDS");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int r = wait_gathers(e, true, true)) return r;
+    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t off_eptr = p.workspace_bytes;
+    const int64_t off_eidx = off_eptr + (with_excl ? align((n_users + 1) * 8) : 0);
+    const size_t need = (size_t)(off_eidx + (with_excl ? align(ex_nnz * 4) : 0));
+    // als_recommend's workspace: both calls are synchronous, so neither is reading it when the other starts
+    if (need > e->d_rec.size()) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const hipError_t st = e->d_rec.reserve(need);
+        if (st != hipSuccess)
+            return fail(ALS_ERR_OUT_OF_MEMORY, "als_rank_targets: device allocation (%zu bytes): %s", need, hipGetErrorString(st));
+    }
+    char* w = e->d_rec.get();
+    int64_t* d_trow = (int64_t*)(w + p.off_trow);
+    int32_t* d_tpos = (int32_t*)(w + p.off_tpos);
+    int32_t* d_tuser = (int32_t*)(w + p.off_tuser);
+    float* d_score = (float*)(w + p.off_score);
+    int32_t* d_rank = (int32_t*)(w + p.off_rank);
+    int64_t* d_m = (int64_t*)(w + p.off_mrows);
+    int64_t* d_eptr = with_excl ? (int64_t*)(w + off_eptr) : nullptr;
+    int32_t* d_eidx = with_excl ? (int32_t*)(w + off_eidx) : nullptr;
+    std::vector<int64_t> eptr0;   // the device ranges index the uploaded slice: rebased to 0
+    hipError_t st = hipMemcpyAsync(d_trow, trow.data(), T * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_tpos, tgt_idx + t0, T * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_m, movie_rows, n_movies * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && with_excl) {
+        st = hipMemcpyAsync(d_tuser, tuser.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+        const int64_t* src = excl_ptr;
+        if (ex0 != 0) {
+            eptr0.resize(n_users + 1);
+            for (int64_t u = 0; u <= n_users; ++u) eptr0[u] = excl_ptr[u] - ex0;
+            src = eptr0.data();
+        }
+        if (st == hipSuccess) st = hipMemcpyAsync(d_eptr, src, (n_users + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+        if (st == hipSuccess && ex_nnz > 0)
+            st = hipMemcpyAsync(d_eidx, excl_idx + ex0, ex_nnz * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    }
+    if (st == hipSuccess)
+        st = cfk::launch_score_pairs(e->precision, U.ptr, M.ptr, e->kp, e->k, d_trow, d_tpos, d_m, T, d_score, e->stream);
+    if (st == hipSuccess && host_rank)
+        st = cfk::launch_rank(e->precision, U.ptr, M.ptr, e->kp, e->k, d_trow, d_tpos, d_tuser, d_score, T, d_m, n_movies, p,
+                              d_eptr, d_eidx, d_rank, e->stream);
+    if (st == hipSuccess) st = hipMemcpyAsync(host_score, d_score, T * sizeof(float), hipMemcpyDeviceToHost, e->stream);
+    if (st == hipSuccess && host_rank)
+        st = hipMemcpyAsync(host_rank, d_rank, T * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
+    // the host arrays are pageable: the stream has to pass the copies before this call returns
+    const hipError_t st2 = hipStreamSynchronize(e->stream);
+    if (st == hipSuccess) st = st2;
+    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_rank_targets: %s", hipGetErrorString(st));
     return sync_checked(e);
 }
 

@@ -1,5 +1,5 @@
 // Internal declarations shared by the engine (als_engine*.cpp, their state: als_engine_impl.h) and the kernels
-// (als_kernels.hip, als_recommend.hip, als_build.hip).
+// (als_kernels.hip, als_recommend.hip, als_rank.hip, als_build.hip).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -125,6 +125,17 @@ hipError_t launch_recommend(int precision, const void* U, const void* M, int kp,
                             int64_t n_users, const int64_t* mrows, int64_t n_cand, int top_n,
                             const RecommendPlan& plan, const int64_t* excl_ptr, const int32_t* excl_idx,
                             float* part_score, int32_t* part_pos, float* out_score, int32_t* out_pos, hipStream_t s);
+// Held-out evaluation (als_rank.hip), all arrays on the device. Target entry t = (factor row trow[t] of its user,
+// candidate position tpos[t], query-user index tuser[t]). launch_score_pairs: score[t] = the same dot for the pair.
+// launch_rank: rank[t] = candidates that come before the target under als_recommend's order (tscore = the scores just
+// computed), minus the excluded ones among them (excl_ptr / excl_idx: device CSR per query user, or both NULL; tuser
+// is read only with exclusions).
+hipError_t launch_score_pairs(int precision, const void* U, const void* M, int kp, int k, const int64_t* trow,
+                              const int32_t* tpos, const int64_t* mrows, int64_t n_tgt, float* score, hipStream_t s);
+hipError_t launch_rank(int precision, const void* U, const void* M, int kp, int k, const int64_t* trow,
+                       const int32_t* tpos, const int32_t* tuser, const float* tscore, int64_t n_tgt,
+                       const int64_t* mrows, int64_t n_cand, const RankPlan& plan, const int64_t* excl_ptr,
+                       const int32_t* excl_idx, int32_t* rank, hipStream_t s);
 hipError_t launch_sq_error(int precision, int kp, const SqErrArgs& a, hipStream_t s);
 // Per-lane accumulator words (elements of the engine precision) of one partial slot: nacc * 64.
 int partial_words_per_lane(int precision, int kp, Path path);

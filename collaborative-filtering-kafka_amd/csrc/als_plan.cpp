@@ -397,4 +397,33 @@ RecommendPlan recommend_plan(int64_t n_users, int64_t n_cand, int top_n, int kp,
     return p;
 }
 
+RankPlan rank_plan(int64_t n_targets, int64_t n_cand, int kp, int cu_count) {
+    (void)kp;
+    RankPlan p;
+    n_targets = std::max<int64_t>(n_targets, 0);
+    n_cand = std::max<int64_t>(n_cand, 0);
+    const int64_t cus = std::max(1, cu_count);
+    p.tgt_tiles = (n_targets + RANK_TGT_TILE - 1) / RANK_TGT_TILE;
+    const int64_t cand_tiles = std::max<int64_t>(1, (n_cand + RANK_CAND_TILE - 1) / RANK_CAND_TILE);
+    int64_t S = 1;
+    if (p.tgt_tiles < cus) {
+        const int64_t tt = std::max<int64_t>(1, p.tgt_tiles);
+        S = std::min({cand_tiles, (RANK_WG_PER_CU * cus + tt - 1) / tt, RANK_MAX_SEGMENTS});
+    }
+    const int64_t seg_tiles = (cand_tiles + S - 1) / S;
+    p.segments = (cand_tiles + seg_tiles - 1) / seg_tiles;   // no empty segment
+    p.seg_len = seg_tiles * RANK_CAND_TILE;
+    p.lds_bytes = rank_lds_bytes();
+    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
+    int64_t off = 0;
+    p.off_trow = off, off += align(n_targets * 8);
+    p.off_tpos = off, off += align(n_targets * 4);
+    p.off_tuser = off, off += align(n_targets * 4);
+    p.off_score = off, off += align(n_targets * 4);
+    p.off_rank = off, off += align(n_targets * 4);
+    p.off_mrows = off, off += align(n_cand * 8);
+    p.workspace_bytes = off;
+    return p;
+}
+
 }  // namespace cfk

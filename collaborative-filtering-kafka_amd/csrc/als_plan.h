@@ -184,4 +184,36 @@ struct RecommendPlan {
 // REC_FEAT_CHUNK whatever the row length); it is part of the signature so that a kp-dependent tile can come later.
 RecommendPlan recommend_plan(int64_t n_users, int64_t n_cand, int top_n, int kp, int cu_count);
 
+// ---- held-out evaluation: exact target ranks (als_rank.hip) ---------------------------------------------------------
+// The row dimension of a tile is target entries, not users: a 256-thread workgroup owns RANK_TGT_TILE targets (each with
+// its user's factor row) and sweeps the RANK_CAND_TILE-candidate tiles of one candidate segment with the recommend
+// kernel's staging (RANK_FEAT_CHUNK features per pass, row pitch RANK_PITCH). Nothing but the two staged tiles is in
+// LDS: thresholds and counters live in registers.
+constexpr int RANK_TGT_TILE = 64;
+constexpr int RANK_CAND_TILE = 64;
+constexpr int RANK_FEAT_CHUNK = 32;
+constexpr int RANK_PITCH = RANK_FEAT_CHUNK + 1;
+constexpr int RANK_WG_PER_CU = 5;              // als_rank_count's occupancy: 92 VGPRs, 5 waves per SIMD, 16.5 KiB of LDS
+constexpr int64_t RANK_MAX_SEGMENTS = 65535;   // gridDim.y
+constexpr int64_t RANK_LDS_LIMIT = 160 * 1024; // LDS of one gfx950 compute unit
+CFK_HOST_DEVICE constexpr int64_t rank_lds_bytes() {
+    return 4 * (int64_t)(RANK_TGT_TILE + RANK_CAND_TILE) * RANK_PITCH;
+}
+
+struct RankPlan {
+    int tgt_tile = RANK_TGT_TILE, cand_tile = RANK_CAND_TILE;
+    int64_t tgt_tiles = 0;      // workgroups along the targets (gridDim.x: no 65535 limit)
+    int64_t segments = 1;       // S: candidate segments (gridDim.y); > 1: one integer atomicAdd per (target, segment)
+    int64_t seg_len = 0;        // candidates per segment: whole candidate tiles, the last segment may be short
+    int64_t lds_bytes = 0;      // dynamic LDS of one workgroup
+    // byte offsets into the call's workspace (256-byte aligned): per target its user's factor row (int64), candidate
+    // position, query-user index (int32), score (float) and rank (int32); then the candidate rows (int64)
+    int64_t off_trow = 0, off_tpos = 0, off_tuser = 0, off_score = 0, off_rank = 0, off_mrows = 0;
+    int64_t workspace_bytes = 0;   // all of the above (the exclusion CSR comes on top, as in als_recommend)
+};
+// Pure function of its arguments. S = 1 when the target tiles alone give every compute unit a workgroup; otherwise the
+// candidate tiles are cut so that target tiles x S reaches RANK_WG_PER_CU workgroups per compute unit, at least one
+// candidate tile per segment. kp does not enter today (as in recommend_plan).
+RankPlan rank_plan(int64_t n_targets, int64_t n_cand, int kp, int cu_count);
+
 }  // namespace cfk

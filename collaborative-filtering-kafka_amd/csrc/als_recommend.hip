@@ -2,25 +2,21 @@
 // movies matrix of als_predict is never written anywhere.
 //
 // Score of (query user u, candidate position c) = als_predict's cell: the Java-float dot of U[user_rows[u]] and
-// M[movie_rows[c]] (FeatureCollector.java:90-101, EJML multTransB): fp32, product and partial sum rounded separately,
-// features 0..k-1 in order, f64 factors narrowed to float first. So the hot loop is VALU with contraction off -- an f32
-// MFMA rounds once per step -- and, like als_predict_kernel's, it runs over the k features, not the padded stride.
+// M[movie_rows[c]], computed tile by tile by als_score_tile.h (shared with als_rank.hip).
 // Order (total): the higher score first, compared as floats (-0 == +0), equal scores by the smaller position c. The
 // result therefore does not depend on tiles, segments or the order in which lanes insert.
 #include <climits>
 #include <cmath>
 
 #include "als_internal.h"
+#include "als_score_tile.h"
 
 namespace cfk {
 namespace {
 
-constexpr int TU = REC_USER_TILE, TC = REC_CAND_TILE, FC = REC_FEAT_CHUNK, PITCH = REC_PITCH, QCAP = REC_QUEUE;
-static_assert(TU == 64 && TC == 64, "a 16 x 16 thread grid of 4 x 4 cells");
+constexpr int TU = score_tile::TR, TC = score_tile::TC, PITCH = score_tile::PITCH, QCAP = REC_QUEUE;
+using score_tile::better;
 static_assert(QCAP <= 64 && REC_MAX_TOP_N <= 64, "one queue entry and one list entry per lane of the merging wave");
-
-// (s, p) comes before (ts, tp) in the result order. False whenever s is NaN.
-__device__ __forceinline__ bool better(float s, int p, float ts, int tp) { return s > ts || (s == ts && p < tp); }
 
 __device__ __forceinline__ float lane_f(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -95,9 +91,7 @@ struct RecArgs {
 };
 
 // Workgroup (blockIdx.x, blockIdx.y) = (user tile, candidate segment). Thread (ty, tx) of the 16 x 16 grid owns the
-// cells of users ty + 16 i and candidates tx + 16 j (i, j < 4): the 16 candidate rows a wave reads in one step are
-// PITCH = 33 words apart (16 banks), its 4 user rows are broadcasts. 16 independent accumulator chains per thread give
-// the ILP; each chain is strictly in feature order across the staged chunks.
+// cells of users ty + 16 i and candidates tx + 16 j (i, j < 4), scored by score_tile::score.
 template <class T>
 __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
     extern __shared__ __attribute__((aligned(16))) float rsm[];
@@ -122,7 +116,6 @@ __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
     const T* U = (const T*)a.U;
     const T* M = (const T*)a.M;
     const int k = a.k;
-    const int n_chunks = (k + FC - 1) / FC;
 
     for (int i = tid; i < TU * n; i += 256) {
         ls[i] = -INFINITY;
@@ -136,8 +129,8 @@ __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
     }
     if (tid == 0) *over = 0;
 
-    // staging: thread -> feature sf of rows sr + 8 r (a wave loads two 128-byte row pieces per step)
-    const int sf = tid & 31, sr = tid >> 5;
+    // staging (score_tile::score): this thread loads one feature of rows sr + 8 r
+    const int sr = tid >> 5;
     const T* urow[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -182,40 +175,7 @@ __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
             mrow[r] = c < seg_end ? M + a.mrows[c] * (int64_t)a.kp : nullptr;
         }
         float acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-        for (int ch = 0; ch < n_chunks; ++ch) {
-            const int f0 = ch * FC;
-            const int fc = min(FC, k - f0);
-            const bool stage_u = n_chunks > 1 || c0 == seg_begin;
-            __syncthreads();   // the previous pass has read its tiles (first pass: the initial state is written)
-            if (sf < fc) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int row = sr + 8 * r;
-                    if (stage_u) su[row * PITCH + sf] = urow[r] ? (float)urow[r][f0 + sf] : 0.f;
-                    sm[row * PITCH + sf] = mrow[r] ? (float)mrow[r][f0 + sf] : 0.f;
-                }
-            }
-            __syncthreads();
-            {
-#pragma clang fp contract(off)
-                for (int f = 0; f < fc; ++f) {
-                    float uv[4], mv[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) uv[i] = su[(ty + 16 * i) * PITCH + f];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) mv[j] = sm[(tx + 16 * j) * PITCH + f];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] + uv[i] * mv[j];   // rounded product, rounded sum
-                }
-            }
-        }
+        score_tile::score(acc, su, sm, urow, mrow, k, c0 == seg_begin, tid);
 
         // selection: a cell that does not come before its user's threshold is dropped here; the exclusion list is
         // consulted only for the survivors, and excluded ones never reach the queue (so they cannot raise the threshold)

@@ -439,6 +439,48 @@ class ALSEngine:
         call("als_recommend_plan", self._h, int(n_users), int(n_movies), int(top_n), v)
         return {"user_tile": v[0], "segments": v[1], "segment_len": v[2], "lds_bytes": v[3]}
 
+    def rank_targets(self, user_rows, movie_rows, targets, exclude=None,
+                     ranks: bool = True) -> tuple[np.ndarray, np.ndarray | None]:
+        """Held-out evaluation (als_rank_targets). targets = (tgt_ptr, tgt_idx): tgt_idx[tgt_ptr[u]:tgt_ptr[u + 1]] =
+        the positions in movie_rows to evaluate for query user u (any order, repeats allowed). Returns (score float32
+        [T], rank int32 [T]) indexed by the target entry counted from tgt_ptr[0]: score = predict()'s cell bit for bit,
+        rank = the number of non-excluded candidates that come before the target under recommend()'s order (0-based).
+        exclude as in recommend(). ranks=False: scores only (no candidate sweep), rank is None."""
+        ur = np.ascontiguousarray(user_rows, np.int64)
+        mr = np.ascontiguousarray(movie_rows, np.int64)
+        tp = np.ascontiguousarray(targets[0], np.int64)
+        ti = np.ascontiguousarray(targets[1], np.int32)
+        if len(tp) != len(ur) + 1:
+            raise ValueError("targets: tgt_ptr must have len(user_rows) + 1 entries")
+        if int(tp[-1]) > len(ti) or int(tp[0]) < 0:
+            raise ValueError("targets: tgt_ptr points outside tgt_idx")
+        T = max(int(tp[-1]) - int(tp[0]), 0)
+        score = np.zeros(T, np.float32)
+        rank = np.zeros(T, np.int32) if ranks else None
+        if ti.size == 0:
+            ti = np.zeros(1, np.int32)       # a valid pointer for an empty list
+        ep = ei = None
+        if exclude is not None:
+            ep = np.ascontiguousarray(exclude[0], np.int64)
+            ei = np.ascontiguousarray(exclude[1], np.int32)
+            if len(ep) != len(ur) + 1:
+                raise ValueError("exclude: excl_ptr must have len(user_rows) + 1 entries")
+            if len(ep) and int(ep[-1]) > len(ei):
+                raise ValueError("exclude: excl_ptr points past excl_idx")
+            if ei.size == 0:
+                ei = np.zeros(1, np.int32)
+        call("als_rank_targets", self._h, ptr(ur, ctypes.c_int64), len(ur), ptr(mr, ctypes.c_int64), len(mr),
+             ptr(tp, ctypes.c_int64), ptr(ti, ctypes.c_int32),
+             ptr(ep, ctypes.c_int64) if ep is not None else None, ptr(ei, ctypes.c_int32) if ei is not None else None,
+             ptr(score, ctypes.c_float), ptr(rank, ctypes.c_int32) if ranks else None)
+        return score, rank
+
+    def rank_plan(self, n_targets: int, n_movies: int) -> dict:
+        """Launch shape rank_targets() would choose (als_rank_plan)."""
+        v = (ctypes.c_int64 * 4)()
+        call("als_rank_plan", self._h, int(n_targets), int(n_movies), v)
+        return {"target_tile": v[0], "segments": v[1], "segment_len": v[2], "lds_bytes": v[3]}
+
     def sq_error(self, side="movie"):
         se = ctypes.c_double()
         cnt = ctypes.c_int64()

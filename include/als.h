@@ -198,6 +198,37 @@ int als_recommend(als_engine* e, const int64_t* user_rows, int64_t n_users, cons
  * lists per segment, merged by a second kernel), [2] = candidates per segment, [3] = dynamic LDS bytes per workgroup. */
 int als_recommend_plan(const als_engine* e, int64_t n_users, int64_t n_movies, int top_n, int64_t info[4]);
 
+/* Held-out evaluation from the resident factors (no reference counterpart): for given (user, candidate) pairs -- the
+ * targets -- the exact score and the exact rank of the target among the user's candidates. One candidate sweep on the
+ * GPU counts what comes before each target; nothing dense is written and nothing is sorted. The rank gives HR@N,
+ * NDCG@N, MRR and the percentile rank for every N at once.
+ *  - user_rows, movie_rows, excl_ptr, excl_idx: exactly as in als_recommend (n_movies < 2^31; exclusions strictly
+ *    ascending per user, in [0, n_movies), checked on the host in O(nnz); both NULL: nothing excluded; exactly one NULL
+ *    is an error).
+ *  - tgt_idx[tgt_ptr[u] .. tgt_ptr[u + 1]) = the candidate positions (indices into movie_rows) to evaluate for query
+ *    user u: any order, repeats allowed, possibly none. Both pointers are required. T = tgt_ptr[n_users] - tgt_ptr[0]
+ *    must be below 2^31; a tgt_ptr[0] != 0 is rebased, and the outputs are indexed by the rebased entry t in [0, T).
+ *    A decreasing tgt_ptr or a position outside [0, n_movies) is ALS_ERR_INVALID_ARGUMENT, naming the user.
+ *  - host_score[t] = exactly als_predict's cell for (user row, movie_rows[target]), bit for bit: the number als_recommend
+ *    reports for that cell.
+ *  - host_rank[t] = the number of candidate positions c in [0, n_movies) that are not excluded for that user and come
+ *    before the target under als_recommend's order: score(c) > score(target) as floats, or equal scores and c < target.
+ *    The rank is 0-based. The target never counts itself. The other targets of the same user count like any candidate:
+ *    each held-out item is ranked against everything the user has not seen. A target that is itself excluded is still
+ *    ranked against the non-excluded candidates.
+ *  - host_rank == NULL: scores only -- no candidate sweep, T dots (the held-out RMSE path).
+ *  - NaN factors are out of contract, as in als_recommend.
+ * Synchronous, on the engine's stream, after pending all-gathers. n_users == 0, T == 0, or n_movies == 0 with ranks
+ * requested: ALS_OK, outputs untouched. Uses als_recommend's grow-only workspace (both calls are synchronous): a call
+ * between two chunks of one half leaves the half's prepared pre-split table and partial slots intact. */
+int als_rank_targets(als_engine* e, const int64_t* user_rows, int64_t n_users, const int64_t* movie_rows, int64_t n_movies,
+                     const int64_t* tgt_ptr, const int32_t* tgt_idx, const int64_t* excl_ptr, const int32_t* excl_idx,
+                     float* host_score, int32_t* host_rank);
+/* Launch shape als_rank_targets would choose for n_targets target entries: info[0] = targets per workgroup tile, [1] =
+ * candidate segments S (> 1: one integer atomic add per target and segment), [2] = candidates per segment, [3] = dynamic
+ * LDS bytes per workgroup. */
+int als_rank_plan(const als_engine* e, int64_t n_targets, int64_t n_movies, int64_t info[4]);
+
 /* Sum of (r - x_row . y_col)^2 over the block's observed ratings and their count (the RMSE/MSE
  * reduction of scripts/calculate_mse.py:78-90 computed on the device from the factors). Synchronous. */
 int als_sq_error(als_engine* e, int side, double* sum_sq_error, int64_t* count);
