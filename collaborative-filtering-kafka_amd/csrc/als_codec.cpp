@@ -9,22 +9,15 @@
 // 106-132: one message per (entity, partition of its out-block), dependent ids filtered by id % P == partition.
 #include <cstdint>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "als.h"
+#include "als_error.h"
 #include "als_host.h"
 
-namespace cfk_detail {
-void set_last_error(const std::string& s);
-}
+using namespace cfk_detail;
 
 namespace {
-
-int err(int code, const char* msg) {
-    cfk_detail::set_last_error(msg);
-    return code;
-}
 
 inline void put32(uint8_t* p, uint32_t v) {
     p[0] = (uint8_t)(v >> 24);
@@ -52,10 +45,10 @@ int64_t als_feature_message_size(int64_t n_deps, int num_features) { return 4 + 
 int als_feature_message_encode(int32_t id, const int32_t* deps, int64_t n_deps, const float* features, int num_features,
                                uint8_t* out, int64_t capacity, int64_t* length) {
     if (n_deps < 0 || n_deps > INT32_MAX || num_features < 0 || (n_deps > 0 && !deps) || (num_features > 0 && !features))
-        return err(ALS_ERR_INVALID_ARGUMENT, "als_feature_message_encode: bad arguments");
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_feature_message_encode: bad arguments");
     const int64_t need = als_feature_message_size(n_deps, num_features);
     if (length) *length = need;
-    if (!out || capacity < need) return err(ALS_ERR_INVALID_ARGUMENT, "als_feature_message_encode: buffer too small");
+    if (!out || capacity < need) return fail(ALS_ERR_INVALID_ARGUMENT, "als_feature_message_encode: buffer too small");
     uint8_t* p = out;
     put32(p, (uint32_t)id);
     p += 4;
@@ -70,19 +63,19 @@ int als_feature_message_encode(int32_t id, const int32_t* deps, int64_t n_deps, 
 
 int als_feature_message_decode(const uint8_t* data, int64_t length, int num_features, int32_t* id, int32_t* deps,
                                int64_t deps_capacity, int64_t* n_deps, float* features) {
-    if (!data || num_features < 0) return err(ALS_ERR_INVALID_ARGUMENT, "als_feature_message_decode: bad arguments");
+    if (!data || num_features < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_feature_message_decode: bad arguments");
     // FeatureMessageDeserializer.java:33-35: the feature list is 4 * (1 + NUM_FEATURES) bytes at the end
     const int64_t feat_bytes = 4 * (1 + (int64_t)num_features);
     const int64_t dep_bytes = length - 4 - feat_bytes;
-    if (dep_bytes < 4) return err(ALS_ERR_PARSE, "FeatureMessage shorter than id + list size + features");
+    if (dep_bytes < 4) return fail(ALS_ERR_PARSE, "FeatureMessage shorter than id + list size + features");
     const int64_t nd = (int32_t)get32(data + 4);
-    if (nd < 0 || 4 + 4 * nd != dep_bytes) return err(ALS_ERR_PARSE, "FeatureMessage dependent-id list length mismatch");
+    if (nd < 0 || 4 + 4 * nd != dep_bytes) return fail(ALS_ERR_PARSE, "FeatureMessage dependent-id list length mismatch");
     if ((int32_t)get32(data + 4 + dep_bytes) != num_features)
-        return err(ALS_ERR_PARSE, "FeatureMessage feature count differs from NUM_FEATURES");
+        return fail(ALS_ERR_PARSE, "FeatureMessage feature count differs from NUM_FEATURES");
     if (id) *id = (int32_t)get32(data);
     if (n_deps) *n_deps = nd;
     if (deps) {
-        if (deps_capacity < nd) return err(ALS_ERR_INVALID_ARGUMENT, "dependent-id buffer too small");
+        if (deps_capacity < nd) return fail(ALS_ERR_INVALID_ARGUMENT, "dependent-id buffer too small");
         for (int64_t i = 0; i < nd; ++i) deps[i] = (int32_t)get32(data + 8 + 4 * i);
     }
     if (features) {
@@ -96,7 +89,7 @@ int als_feature_message_decode(const uint8_t* data, int64_t length, int num_feat
 }
 
 int als_id_rating_encode(int32_t id, int16_t rating, uint8_t* out6) {
-    if (!out6) return err(ALS_ERR_INVALID_ARGUMENT, "als_id_rating_encode: out is NULL");
+    if (!out6) return fail(ALS_ERR_INVALID_ARGUMENT, "als_id_rating_encode: out is NULL");
     put32(out6, (uint32_t)id);
     out6[4] = (uint8_t)((uint16_t)rating >> 8);
     out6[5] = (uint8_t)rating;
@@ -104,7 +97,7 @@ int als_id_rating_encode(int32_t id, int16_t rating, uint8_t* out6) {
 }
 
 int als_id_rating_decode(const uint8_t* data, int64_t length, int32_t* id, int16_t* rating) {
-    if (!data || length != 6) return err(ALS_ERR_PARSE, "IdRatingPairMessage must be 6 bytes");
+    if (!data || length != 6) return fail(ALS_ERR_PARSE, "IdRatingPairMessage must be 6 bytes");
     if (id) *id = (int32_t)get32(data);
     if (rating) *rating = (int16_t)(((uint16_t)data[4] << 8) | data[5]);
     return ALS_OK;
@@ -115,7 +108,7 @@ int als_encode_feature_messages(const als_dataset* ds, int side, int n_partition
                                 int64_t* n_messages, int32_t* keys, int64_t* offsets, int64_t messages_capacity) {
     if (!ds || (side != ALS_SIDE_MOVIE && side != ALS_SIDE_USER) || n_partitions < 1 || n_partitions > INT16_MAX ||
         num_features < 0 || (out && (!factors || ld < num_features)))
-        return err(ALS_ERR_INVALID_ARGUMENT, "als_encode_feature_messages: bad arguments");
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_encode_feature_messages: bad arguments");
     int64_t counts[2] = {0, 0}, nnz = 0;
     int rc = als_dataset_counts(ds, &counts[ALS_SIDE_MOVIE], &counts[ALS_SIDE_USER], &nnz);
     if (rc != ALS_OK) return rc;
@@ -137,9 +130,9 @@ int als_encode_feature_messages(const als_dataset* ds, int side, int n_partition
             if (length) *length = total;
             if (n_messages) *n_messages = n_msg;
             if (!out) return ALS_OK;   // size query
-            if (capacity < total) return err(ALS_ERR_INVALID_ARGUMENT, "message buffer too small");
+            if (capacity < total) return fail(ALS_ERR_INVALID_ARGUMENT, "message buffer too small");
             if ((keys || offsets) && messages_capacity < n_msg)
-                return err(ALS_ERR_INVALID_ARGUMENT, "key/offset arrays too small");
+                return fail(ALS_ERR_INVALID_ARGUMENT, "key/offset arrays too small");
             total = 0;
             n_msg = 0;
         }

@@ -2,31 +2,13 @@
 // lifetime, the environment, streams, synchronisation and the integrity record, timing, introspection. See
 // include/als.h for the reference interface each entry point replaces.
 #include <chrono>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <memory>
 #include <thread>
 
 #include "als_engine_impl.h"
 
-namespace {
-thread_local std::string g_last_error;
-}
-
 namespace cfk_detail {
-
-void set_last_error(const std::string& s) { g_last_error = s; }
-
-int fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
 
 int check_engine(const als_engine* e) {
     if (!e) return fail(ALS_ERR_INVALID_ARGUMENT, "engine is NULL");
@@ -181,7 +163,6 @@ int als_device_count(int* n) {
     HIP_TRY(hipGetDeviceCount(n));
     return ALS_OK;
 }
-const char* als_last_error(void) { return g_last_error.c_str(); }
 
 #define CFK_STR2(x) #x
 #define CFK_STR(x) CFK_STR2(x)

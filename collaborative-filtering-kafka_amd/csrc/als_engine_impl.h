@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "als.h"
+#include "als_error.h"
 #include "als_internal.h"
 #include "als_resources.h"
 
@@ -20,9 +21,6 @@ namespace cfk_detail {
 using cfk::DeviceBuf;
 using cfk::Path;
 using cfk::Task;
-
-// Sets the thread's als_last_error() message and returns `code`.
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \

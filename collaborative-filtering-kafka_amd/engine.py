@@ -3,7 +3,8 @@
 Reference interface (paths under src/main/java/de/hpi/collaborativefilteringkafka/):
   - ``Dataset``           ingest + in-block build + partition key: producers/NetflixDataFormatProducer.java:44-60,
                           processors/MRatings2BlocksProcessor.java:48-69, processors/URatings2BlocksProcessor.java:72-92,
-                          producers/PureModStreamPartitioner.java:9-10 (all computed natively in als_dataset.cpp)
+                          producers/PureModStreamPartitioner.java:9-10 (all computed natively in als_dataset.cpp and
+                          als_dataset_shard.cpp)
   - ``ALSEngine``         one partition's MFeatureCalculator / UFeatureCalculator solve state
                           (processors/MFeatureCalculator.java:49-136, processors/UFeatureCalculator.java:49-136)
 
