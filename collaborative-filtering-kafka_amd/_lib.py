@@ -88,6 +88,8 @@ SIGNATURES = [
     ("als_recommend_plan", _i, [_vp, _i64, _i64, _i, _pi64]),
     ("als_rank_targets", _i, [_vp, _pi64, _i64, _pi64, _i64, _pi64, _pi32, _pi64, _pi32, _pf, _pi32]),
     ("als_rank_plan", _i, [_vp, _i64, _i64, _pi64]),
+    ("als_fold_in", _i, [_vp, _i, _i64, _pi64, _pi32, _pi16, _f, _pi64, _vp, _i64]),
+    ("als_fold_in_plan", _i, [_vp, _i64, _pi64]),
     ("als_sq_error", _i, [_vp, _i, _pd, _pi64]),
     ("als_synchronize", _i, [_vp]),
     ("als_integrity_status", _i, [_vp, ctypes.POINTER(ctypes.c_uint32), _i]),

@@ -108,6 +108,47 @@ def heldout_queries(ds: Dataset, movie_ids, user_ids, world: int, rank: int, mov
     return tgt_ptr, pos.astype(np.int32), own.astype(np.int64), seen, int(len(u) - len(own)), int(seen.sum())
 
 
+def foldin_queries(ds: Dataset, world: int, movie_rows, users):
+    """What ALSEngine.fold_in and a following ALSEngine.recommend need for users that are not in `ds`. users: one
+    sequence of (movie id, rating) pairs per new user. Returns (q_ptr, q_idx, q_ratings, excl_ptr, excl_idx, n_unknown):
+    q_idx[q_ptr[i]:q_ptr[i + 1]] = the movie factor rows (slots under `world` shards) of user i's rated movies with their
+    ratings, in input order (a movie listed twice counts twice, as als_set_block would count it); n_unknown pairs are
+    skipped because their movie is not in `ds`, and a user with no known movie keeps an empty range (fold-in gives the
+    zero vector). excl_idx[excl_ptr[i]:excl_ptr[i + 1]] = the positions in `movie_rows` (movie factor rows, any subset,
+    repeats allowed: every position of a repeated slot) of those movies, strictly ascending: the exclusion list that
+    keeps recommend from returning what the user has rated; rated movies outside `movie_rows` are dropped from it.
+    Pure host code."""
+    n = len(users)
+    pairs = [np.asarray(u, np.int64).reshape(-1, 2) for u in users]
+    cnt = np.array([len(p) for p in pairs], np.int64)
+    allp = np.concatenate(pairs) if n else np.zeros((0, 2), np.int64)
+    user = np.repeat(np.arange(n, dtype=np.int64), cnt)
+    mid, rat = allp[:, 0], allp[:, 1]
+    if len(rat) and (rat.min() < -32768 or rat.max() > 32767):
+        raise ValueError("ratings must fit a Java short")
+    all_movies = ds.ids(SIDE_MOVIE)
+    slot_of = ds.slots(SIDE_MOVIE, world)
+    mi = np.minimum(np.searchsorted(all_movies, mid), max(len(all_movies) - 1, 0))
+    known = all_movies[mi] == mid if len(all_movies) else np.zeros(len(mid), bool)
+    user, slot, rat = user[known], (slot_of[mi[known]] if len(all_movies) else np.zeros(0, np.int64)), rat[known]
+    q_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(user, minlength=n), out=q_ptr[1:])
+    mr = np.ascontiguousarray(movie_rows, np.int64)
+    order = np.argsort(mr, kind="stable")              # positions grouped by slot: the inverse of movie_rows
+    by_slot = mr[order]
+    lo = np.searchsorted(by_slot, slot, "left")
+    c = np.searchsorted(by_slot, slot, "right") - lo     # 0: not a candidate; > 1: the slot is listed several times
+    eu = np.repeat(user, c)
+    start = np.cumsum(c) - c
+    pos = order[np.repeat(lo, c) + (np.arange(int(c.sum()), dtype=np.int64) - np.repeat(start, c))]
+    key = np.unique(eu * max(len(mr), 1) + pos)          # ascending position inside every user, each once
+    eu, pos = key // max(len(mr), 1), key % max(len(mr), 1)
+    excl_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(eu, minlength=n), out=excl_ptr[1:])
+    return (q_ptr, slot.astype(np.int32), rat.astype(np.int16), excl_ptr, pos.astype(np.int32),
+            int(len(known) - int(known.sum())))
+
+
 def ranking_metrics(rank, n_eligible, top_n: int) -> dict:
     """Ranking quality from exact 0-based ranks (ALSEngine.rank_targets), pure numpy in float64: HR@N = mean(rank < N),
     NDCG@N = mean(1 / log2(rank + 2) where rank < N, else 0), MRR = mean(1 / (rank + 1)), MPR = mean(rank /
@@ -171,8 +212,12 @@ class ALSApp:
 
     # -------------------------------------------------------------------------------------------------
     def setup(self, ds: Dataset, check_duplicates: bool = True, engine_factory=None,
-              block_build: str = "device") -> "ALSApp":
+              block_build: str = "device", spare_user_rows: int = 0) -> "ALSApp":
         """Blocks of this rank's shard + factor replicas + U0 (UFeatureInitializer after the EOF barrier).
+
+        spare_user_rows > 0: that many extra rows of U after all shard slots (and before the sentinel), zero until
+        fold_in / recommend_for put users there that are not in `ds`. They are local to this rank: no half solves them
+        and no all-gather covers them.
 
         ``engine_factory(k, precision, device)`` replaces the HIP engine with another object of the same
         interface; only the multi-rank CPU rehearsal tests (gloo) use it, to exercise the sharding and the
@@ -204,18 +249,21 @@ class ALSApp:
         else:
             eng = engine_factory(self.NUM_FEATURES, self.precision, self.device)
         eng.use_torch_stream()
+        self.spare_user_rows = max(0, int(spare_user_rows))
+        spare = [0, self.spare_user_rows]                   # per side: rows after the shard slots
         for side in (SIDE_MOVIE, SIDE_USER):
             opp = ds.shard_info(1 - side, self.world, self.rank)
+            n_opp = opp["n_slots"] + spare[1 - side]            # the sentinel row follows the spare rows
             if block_build == "device" and hasattr(eng, "set_block_coo"):
                 # block builders on the GPU: arrival-order COO -> stable radix sort by row (als_set_block_coo)
                 blk = ds.shard_coo(side, self.world, self.rank)
-                eng.alloc_factors(side, blk["n_slots"])
+                eng.alloc_factors(side, blk["n_slots"] + spare[side])
                 eng.set_block_coo(side, blk["n_rows"], blk["rows"], blk["cols"], blk["ratings"], blk["row_offset"],
-                                  opp["n_slots"])
+                                  n_opp)
             else:
                 blk = ds.shard_block(side, self.world, self.rank)
-                eng.alloc_factors(side, blk["n_slots"])
-                eng.set_block(side, blk["row_ptr"], blk["col"], blk["ratings"], blk["row_offset"], opp["n_slots"])
+                eng.alloc_factors(side, blk["n_slots"] + spare[side])
+                eng.set_block(side, blk["row_ptr"], blk["col"], blk["ratings"], blk["row_offset"], n_opp)
             sc, nc = ds.slot_layout(side, self.world)
             blk["slots_per_chunk"], blk["n_chunks"] = sc, nc
             if nc > 1:
@@ -313,7 +361,8 @@ class ALSApp:
         compared by MIN/MAX all-reduces. Returns {"replicas_agree", "integrity_clean", "digest": [movie, user],
         "integrity_failures"}; at N = 1 trivially true (one replica)."""
         self.engine.synchronize()
-        digests = [_table_digest(self.engine.factors[s]) for s in (SIDE_MOVIE, SIDE_USER)]
+        # the shard slots only: spare user rows are rank-local (the all-zero sentinel adds nothing to the digest)
+        digests = [_table_digest(self.engine.factors[s][:self.info[s]["n_slots"]]) for s in (SIDE_MOVIE, SIDE_USER)]
         bad = int(self.engine.integrity_status()[0]) if hasattr(self.engine, "integrity_status") else 0
         if self.world == 1 or self.exchange == "none":
             return {"replicas_agree": True, "integrity_clean": bad == 0, "digest": [f"{d:016x}" for d in digests],
@@ -330,7 +379,7 @@ class ALSApp:
 
     def factors(self):
         """(U, M) in ascending raw-id order (FeatureCollector.constructFeatureMatrices, :72-88)."""
-        U = self.engine.read_factors(SIDE_USER)
+        U = self.engine.read_factors(SIDE_USER, 0, self.info[SIDE_USER]["n_slots"])
         M = self.engine.read_factors(SIDE_MOVIE)
         return U[self.ds.slots(SIDE_USER, self.world)], M[self.ds.slots(SIDE_MOVIE, self.world)]
 
@@ -357,6 +406,37 @@ class ALSApp:
             user_ids = user_ids[user_ids % self.world == self.rank]
         out = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
         return user_ids, out.astype(np.int64), score
+
+    def fold_in(self, users, dst_rows=None) -> np.ndarray:
+        """User factors [n, k] of users that are not in the training data, from their (movie id, rating) lists and the
+        resident movie factors (ALSEngine.fold_in with this app's lambda; foldin_queries maps the movie ids and skips
+        unknown ones; a user without a known movie gets zeros). dst_rows: rows of U that also receive them."""
+        movie_rows = self.ds.slots(SIDE_MOVIE, self.world)
+        q_ptr, q_idx, q_rat, _, _, _ = foldin_queries(self.ds, self.world, movie_rows, users)
+        return self.engine.fold_in(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, dst_rows=dst_rows)
+
+    def recommend_for(self, users, top_n: int, exclude_seen: bool = True) -> tuple[np.ndarray, np.ndarray]:
+        """Top-N movies for users that are not in the training data: their (movie id, rating) lists are folded into the
+        spare rows of U (setup(spare_user_rows=...), as many users at a time as there are spare rows) and recommend()
+        runs on those rows against all movies in ascending id. Returns (movie_ids [n, top_n], scores [n, top_n]) as
+        ALSApp.recommend does; exclude_seen leaves out the movies a user has rated."""
+        if self.spare_user_rows < 1:
+            raise ValueError("recommend_for needs spare user rows: setup(..., spare_user_rows=n)")
+        movie_ids = self.ds.ids(SIDE_MOVIE)
+        movie_rows = self.ds.slots(SIDE_MOVIE, self.world)       # ascending id -> factor row
+        base = self.info[SIDE_USER]["n_slots"]
+        n = len(users)
+        out = np.full((n, top_n), -1, np.int64)
+        score = np.full((n, top_n), -np.inf, np.float32)
+        for u0 in range(0, n, self.spare_user_rows):
+            part = users[u0:u0 + self.spare_user_rows]
+            q_ptr, q_idx, q_rat, excl_ptr, excl_idx, _ = foldin_queries(self.ds, self.world, movie_rows, part)
+            rows = base + np.arange(len(part), dtype=np.int64)
+            self.engine.fold_in(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, dst_rows=rows, return_host=False)
+            idx, sc = self.engine.recommend(rows, movie_rows, top_n, (excl_ptr, excl_idx) if exclude_seen else None)
+            out[u0:u0 + len(part)] = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
+            score[u0:u0 + len(part)] = sc
+        return out, score
 
     def evaluate(self, movie_ids, user_ids, ratings, top_n: int = 10, exclude_seen: bool = True,
                  ranks: bool = True) -> dict:

@@ -1,8 +1,10 @@
 // als_engine_solve.cpp -- what runs on the resident factors: factor buffers and their I/O, the half-iteration launch,
-// squared error, predict, recommend and held-out ranks. The steady-state half (launch_half) allocates nothing and creates no stream
+// squared error, predict, recommend, held-out ranks and fold-in. The steady-state half (launch_half) allocates nothing and creates no stream
 // or event: the side stream and its two events are made by the first half that needs them, timing events come from
 // the engine's pool.
 #include "als_engine_impl.h"
+
+#include <unordered_set>
 
 using namespace cfk_detail;
 
@@ -526,6 +528,137 @@ int als_rank_targets(als_engine* e, const int64_t* user_rows, int64_t n_users, c
     const hipError_t st2 = hipStreamSynchronize(e->stream);
     if (st == hipSuccess) st = st2;
     if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_rank_targets: %s", hipGetErrorString(st));
+    return sync_checked(e);
+}
+
+int als_fold_in_plan(const als_engine* e, int64_t n_queries, int64_t info[4]) {
+    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (n_queries < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in_plan: n_queries < 0");
+    if (e->kp > cfk::FOLDIN_MAX_KP)
+        return fail(ALS_ERR_UNSUPPORTED, "als_fold_in: factor stride %d exceeds the supported %d", e->kp, cfk::FOLDIN_MAX_KP);
+    const cfk::FoldinPlan p = cfk::foldin_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
+    info[0] = p.threads;
+    info[1] = p.grid;
+    info[2] = p.batch;
+    info[3] = p.lds_bytes;
+    return ALS_OK;
+}
+
+int als_fold_in(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
+                const int16_t* q_ratings, float lambda, const int64_t* dst_rows, void* host_out, int64_t out_ld) {
+    if (int r = check_engine(e)) return r;
+    if (int r = check_side(side)) return r;
+    if (n_queries < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: n_queries < 0");
+    if (e->kp > cfk::FOLDIN_MAX_KP)
+        return fail(ALS_ERR_UNSUPPORTED, "als_fold_in: factor stride %d exceeds the supported %d", e->kp, cfk::FOLDIN_MAX_KP);
+    const Factors& self = e->fac[side];
+    const Factors& opp = e->fac[1 - side];
+    if (!opp.ptr) return fail(ALS_ERR_STATE, "als_fold_in: factors of side %d (the opposite side) not allocated/bound", 1 - side);
+    if (dst_rows && !self.ptr) return fail(ALS_ERR_STATE, "als_fold_in: dst_rows given but factors of side %d not allocated/bound", side);
+    if (n_queries == 0) return ALS_OK;
+    if (!q_ptr || !q_idx || !q_ratings) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: q_ptr, q_idx and q_ratings must be given");
+    if (!dst_rows && !host_out) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: dst_rows and host_out are both NULL");
+    if (host_out && out_ld < e->k)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: out_ld (%lld) < num_features (%d)", (long long)out_ld, e->k);
+    if (!(lambda >= 0.f)) return fail(ALS_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
+    const int64_t p0 = q_ptr[0];
+    if (p0 < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: q_ptr[0] is negative");
+    for (int64_t q = 0; q < n_queries; ++q)
+        if (q_ptr[q + 1] < q_ptr[q])
+            return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: q_ptr decreases at query %lld", (long long)q);
+    const int64_t nnz = q_ptr[n_queries] - p0;
+    if (nnz > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: the number of entries must be below 2^31");
+    for (int64_t q = 0; q < n_queries; ++q)
+        for (int64_t x = q_ptr[q]; x < q_ptr[q + 1]; ++x)
+            if (q_idx[x] < 0 || q_idx[x] >= opp.n_rows)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: index %d of query %lld is outside [0, %lld)", (int)q_idx[x],
+                            (long long)q, (long long)opp.n_rows);
+    if (dst_rows) {
+        std::unordered_set<int64_t> seen;
+        seen.reserve((size_t)n_queries * 2);
+        for (int64_t q = 0; q < n_queries; ++q) {
+            if (dst_rows[q] < 0 || dst_rows[q] >= self.n_rows)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: dst_rows[%lld] = %lld of query %lld is outside [0, %lld)",
+                            (long long)q, (long long)dst_rows[q], (long long)q, (long long)self.n_rows);
+            if (!seen.insert(dst_rows[q]).second)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: dst_rows repeats row %lld at query %lld",
+                            (long long)dst_rows[q], (long long)q);
+        }
+    }
+    const cfk::FoldinPlan p = cfk::foldin_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
+    if (p.lds_bytes > cfk::FOLDIN_LDS_LIMIT) return fail(ALS_ERR_UNSUPPORTED, "als_fold_in: launch plan exceeds the LDS");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int r = wait_gathers(e, true, true)) return r;
+    // workspace (256-byte aligned): rebased ranges, indices, ratings, destination rows, the kp-wide result rows
+    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const size_t row_bytes = (size_t)e->kp * e->elem();
+    const int64_t off_ptr = 0;
+    const int64_t off_idx = off_ptr + align((n_queries + 1) * 8);
+    const int64_t off_rat = off_idx + align(nnz * 4);
+    const int64_t off_dst = off_rat + align(nnz * 2);
+    const int64_t off_out = off_dst + (dst_rows ? align(n_queries * 8) : 0);
+    const size_t need = (size_t)off_out + (size_t)n_queries * row_bytes;
+    // als_recommend's workspace: all three calls are synchronous, so none is reading it when another starts
+    if (need > e->d_rec.size()) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const hipError_t st = e->d_rec.reserve(need);
+        if (st != hipSuccess)
+            return fail(ALS_ERR_OUT_OF_MEMORY, "als_fold_in: device allocation (%zu bytes): %s", need, hipGetErrorString(st));
+    }
+    char* w = e->d_rec.get();
+    std::vector<int64_t> ptr0;   // the device ranges index the uploaded slice: rebased to 0
+    const int64_t* src = q_ptr;
+    if (p0 != 0) {
+        ptr0.resize(n_queries + 1);
+        for (int64_t q = 0; q <= n_queries; ++q) ptr0[q] = q_ptr[q] - p0;
+        src = ptr0.data();
+    }
+    cfk::FoldinArgs a{};
+    a.opp = opp.ptr;
+    a.self = self.ptr;
+    a.out = w + off_out;
+    a.q_ptr = (const int64_t*)(w + off_ptr);
+    a.q_idx = (const int32_t*)(w + off_idx);
+    a.q_rat = (const int16_t*)(w + off_rat);
+    a.dst_rows = dst_rows ? (const int64_t*)(w + off_dst) : nullptr;
+    a.n_queries = n_queries;
+    a.k = e->k;
+    a.lambda = lambda;
+    hipError_t st = hipMemcpyAsync(w + off_ptr, src, (n_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && nnz > 0)
+        st = hipMemcpyAsync(w + off_idx, q_idx + p0, nnz * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && nnz > 0)
+        st = hipMemcpyAsync(w + off_rat, q_ratings + p0, nnz * sizeof(int16_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && dst_rows)
+        st = hipMemcpyAsync(w + off_dst, dst_rows, n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    // read back the way als_read_factors does: whole kp-wide rows through the pinned staging buffer, the first k columns
+    // kept; a result that fits the buffer is queued behind the kernel, so the call waits for the stream once
+    const size_t es = e->elem();
+    int64_t rows_per = 0;
+    if (host_out) {
+        if (int r = ensure_stage(e)) return r;
+        rows_per = (int64_t)(e->h_stage.bytes() / row_bytes);
+    }
+    const bool one_pass = host_out && n_queries <= rows_per;
+    if (st == hipSuccess) st = cfk::launch_fold_in(e->precision, e->kp, a, p, e->stream);
+    if (st == hipSuccess && one_pass)
+        st = cfk::launch_download(w + off_out, e->h_stage.get(), (size_t)n_queries * row_bytes, e->stream);
+    // the host arrays (ptr0 too) are pageable: the stream has to pass the copies before this call returns
+    const hipError_t st2 = hipStreamSynchronize(e->stream);
+    if (st == hipSuccess) st = st2;
+    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_fold_in: %s", hipGetErrorString(st));
+    for (int64_t r = 0; host_out && r < n_queries; r += rows_per) {
+        const int64_t nr = std::min(rows_per, n_queries - r);
+        if (!one_pass) {
+            HIP_TRY(cfk::launch_download(w + off_out + (size_t)r * row_bytes, e->h_stage.get(), (size_t)nr * row_bytes,
+                                         e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        }
+        const char* stage = (const char*)e->h_stage.get();
+        char* dst = (char*)host_out + (size_t)r * out_ld * es;
+        for (int64_t i = 0; i < nr; ++i)
+            std::memcpy(dst + (size_t)i * out_ld * es, stage + i * row_bytes, (size_t)e->k * es);
+    }
     return sync_checked(e);
 }
 

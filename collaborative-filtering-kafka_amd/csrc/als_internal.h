@@ -136,6 +136,23 @@ hipError_t launch_rank(int precision, const void* U, const void* M, int kp, int 
                        const int32_t* tpos, const int32_t* tuser, const float* tscore, int64_t n_tgt,
                        const int64_t* mrows, int64_t n_cand, const RankPlan& plan, const int64_t* excl_ptr,
                        const int32_t* excl_idx, int32_t* rank, hipStream_t s);
+// Fold-in (als_foldin.hip), all arrays on the device: query q solves x = (Y^T Y + lambda n I)^-1 Y^T r over the opposite
+// rows q_idx[q_ptr[q] .. q_ptr[q + 1]) (q_ptr[0] = 0) with the ratings q_rat, n their count; n = 0 gives zeros. Row q of
+// `out` ([n_queries][kp], columns >= k zero) always receives it, and so does row dst_rows[q] of `self` when dst_rows is
+// not NULL. kp: 16, 32, 64 or 128; the geometry is foldin_plan's (als_plan.h).
+struct FoldinArgs {
+    const void* opp;          // opposite factor matrix [n_opp][kp], the plain table
+    void* self;               // this side's factor matrix (read only with dst_rows)
+    void* out;                // [n_queries][kp]
+    const int64_t* q_ptr;     // [n_queries + 1]
+    const int32_t* q_idx;
+    const int16_t* q_rat;
+    const int64_t* dst_rows;  // [n_queries] or NULL
+    int64_t n_queries;
+    int32_t k;
+    float lambda;
+};
+hipError_t launch_fold_in(int precision, int kp, const FoldinArgs& a, const FoldinPlan& plan, hipStream_t s);
 hipError_t launch_sq_error(int precision, int kp, const SqErrArgs& a, hipStream_t s);
 // Per-lane accumulator words (elements of the engine precision) of one partial slot: nacc * 64.
 int partial_words_per_lane(int precision, int kp, Path path);

@@ -426,4 +426,16 @@ RankPlan rank_plan(int64_t n_targets, int64_t n_cand, int kp, int cu_count) {
     return p;
 }
 
+FoldinPlan foldin_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count) {
+    FoldinPlan p;
+    int batch = FOLDIN_MAX_BATCH;
+    while (batch > 4 && foldin_lds_bytes(kp, elem_bytes, batch) > FOLDIN_LDS_LIMIT) batch -= 4;
+    p.batch = batch;
+    p.lds_bytes = foldin_lds_bytes(kp, elem_bytes, batch);
+    const int64_t per_cu =
+        std::min<int64_t>(FOLDIN_MAX_WG_PER_CU, std::max<int64_t>(1, FOLDIN_LDS_LIMIT / std::max<int64_t>(1, p.lds_bytes)));
+    p.grid = std::max<int64_t>(1, std::min<int64_t>(n_queries, per_cu * std::max(1, cu_count)));
+    return p;
+}
+
 }  // namespace cfk

@@ -216,4 +216,35 @@ struct RankPlan {
 // candidate tile per segment. kp does not enter today (as in recommend_plan).
 RankPlan rank_plan(int64_t n_targets, int64_t n_cand, int kp, int cu_count);
 
+// ---- fold-in: factor rows of ad-hoc queries (als_foldin.hip) --------------------------------------------------------
+// One FOLDIN_THREADS workgroup owns one whole query, grid-stride over the queries. Its dynamic LDS, in elements of the
+// engine's type: the Gram's lower-triangle 16 x 16 tiles (row pitch FOLDIN_TILE_PITCH: odd, so a column of the
+// factorisation falls into 16 banks), `batch` staged opposite rows of foldin_pitch(kp) elements (pitch = 16 mod 32: the
+// 4 entries x 16 features one MFMA operand read touches lie in distinct banks), four kp-vectors (Jacobi scale, Cholesky
+// diagonal, substitution broadcast, solution) and the batch's ratings / residuals.
+constexpr int FOLDIN_THREADS = 256;
+constexpr int FOLDIN_MAX_KP = 128;
+constexpr int FOLDIN_MAX_BATCH = 64;
+constexpr int FOLDIN_TILE_PITCH = 17;
+constexpr int FOLDIN_TILE_ELEMS = 16 * FOLDIN_TILE_PITCH;
+constexpr int FOLDIN_MAX_WG_PER_CU = 8;
+constexpr int64_t FOLDIN_LDS_LIMIT = 160 * 1024;   // LDS of one gfx950 compute unit
+CFK_HOST_DEVICE constexpr int foldin_pitch(int kp) { return kp == 16 ? 16 : kp + 16; }
+CFK_HOST_DEVICE constexpr int foldin_tiles(int kp) { return (kp / 16) * (kp / 16 + 1) / 2; }
+CFK_HOST_DEVICE constexpr int64_t foldin_lds_bytes(int kp, int elem_bytes, int batch) {
+    return (int64_t)elem_bytes *
+           ((int64_t)foldin_tiles(kp) * FOLDIN_TILE_ELEMS + (int64_t)batch * foldin_pitch(kp) + 4 * kp + batch);
+}
+
+struct FoldinPlan {
+    int threads = FOLDIN_THREADS;
+    int64_t grid = 1;        // workgroups launched: every compute unit filled to its LDS, never more than the queries
+    int batch = 0;           // opposite rows staged per pass: a multiple of 4 (one MFMA step), at most FOLDIN_MAX_BATCH
+    int64_t lds_bytes = 0;   // dynamic LDS of one workgroup
+};
+// Pure function of its arguments. kp: 16, 32, 64 or 128; elem_bytes: 4 or 8. The batch is the largest that fits the LDS
+// beside the Gram (FOLDIN_MAX_BATCH for every supported shape); the grid is what the compute units hold at that LDS
+// size, at most FOLDIN_MAX_WG_PER_CU each. A query's result does not depend on the grid (one workgroup per query).
+FoldinPlan foldin_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count);
+
 }  // namespace cfk

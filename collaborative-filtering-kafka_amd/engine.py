@@ -482,6 +482,43 @@ class ALSEngine:
         call("als_rank_plan", self._h, int(n_targets), int(n_movies), v)
         return {"target_tile": v[0], "segments": v[1], "segment_len": v[2], "lds_bytes": v[3]}
 
+    def fold_in(self, side, queries, lam: float, dst_rows=None, return_host: bool = True) -> np.ndarray | None:
+        """Factor rows of entities that were not in the training block (als_fold_in). queries = (ptr, idx, ratings):
+        idx[ptr[q]:ptr[q + 1]] = the opposite side's factor rows (slots) query q rated, ratings the int16 ratings, in
+        the order given. Returns the [n, k] solutions x = (Y^T Y + lam n I)^-1 Y^T r (zeros for a query without
+        entries) in the engine's precision, or None with return_host=False. dst_rows: factor rows of `side` that also
+        receive the results on the device (bitwise the returned rows), e.g. spare rows after the trained entities."""
+        qp = np.ascontiguousarray(queries[0], np.int64)
+        qi = np.ascontiguousarray(queries[1], np.int32)
+        qr = np.ascontiguousarray(queries[2], np.int16)
+        if qp.ndim != 1 or len(qp) < 1:
+            raise ValueError("queries: ptr must have n + 1 entries")
+        n = len(qp) - 1
+        if len(qi) != len(qr):
+            raise ValueError("queries: idx and ratings must have the same length")
+        if int(qp[-1]) > len(qi) or int(qp[0]) < 0:
+            raise ValueError("queries: ptr points outside idx")
+        if qi.size == 0:
+            qi, qr = np.zeros(1, np.int32), np.zeros(1, np.int16)   # valid pointers for empty lists
+        dr = None
+        if dst_rows is not None:
+            dr = np.ascontiguousarray(dst_rows, np.int64)
+            if len(dr) != n:
+                raise ValueError("dst_rows must have one entry per query")
+            if dr.size == 0:
+                dr = np.zeros(1, np.int64)
+        out = np.zeros((n, self.k), self.np_dtype) if return_host else None
+        call("als_fold_in", self._h, _side(side), n, ptr(qp, ctypes.c_int64), ptr(qi, ctypes.c_int32),
+             ptr(qr, ctypes.c_int16), float(np.float32(lam)), ptr(dr, ctypes.c_int64) if dr is not None else None,
+             out.ctypes.data_as(ctypes.c_void_p) if out is not None else None, self.k)
+        return out
+
+    def fold_in_plan(self, n_queries: int) -> dict:
+        """Launch shape fold_in() would choose (als_fold_in_plan)."""
+        v = (ctypes.c_int64 * 4)()
+        call("als_fold_in_plan", self._h, int(n_queries), v)
+        return {"threads": v[0], "workgroups": v[1], "batch": v[2], "lds_bytes": v[3]}
+
     def sq_error(self, side="movie"):
         se = ctypes.c_double()
         cnt = ctypes.c_int64()

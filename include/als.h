@@ -229,6 +229,38 @@ int als_rank_targets(als_engine* e, const int64_t* user_rows, int64_t n_users, c
  * LDS bytes per workgroup. */
 int als_rank_plan(const als_engine* e, int64_t n_targets, int64_t n_movies, int64_t info[4]);
 
+/* Fold-in: the factor rows of entities that were not in the training block (a user who turns up after training, or
+ * whose ratings have changed), from their ratings and the opposite side's resident factors, without retraining:
+ * x = (Y^T Y + lambda (float) n I)^-1 Y^T r over the query's n entries -- the normal equation of als_solve_half
+ * (MFeatureCalculator.java:85-99) over ad-hoc rows. No block, no work plan, no per-engine state.
+ *  - side: the entity type being solved (ALS_SIDE_USER: each query is a user). q_idx[q_ptr[q] .. q_ptr[q + 1]) are
+ *    factor rows (slots) of the OPPOSITE side's resident matrix, q_ratings the ratings, typed as in als_set_block.
+ *    Entries are used in the order given; a repeated index counts twice, as als_set_block would count it. A
+ *    q_ptr[0] != 0 is rebased. The total entry count must be below 2^31.
+ *  - A query without entries gives the zero vector, like every other path. lambda as in als_solve_half.
+ *  - host_out, if not NULL: row q at host_out + q * out_ld elements (float for ALS_F32, double for ALS_F64),
+ *    out_ld >= num_features.
+ *  - dst_rows, if not NULL: the result is also stored into factor row dst_rows[q] of `side`'s resident matrix, columns
+ *    >= num_features up to the stride zero, bit for bit the host result. No other row and never the sentinel row is
+ *    touched. Entries lie in [0, n_total_rows) and do not repeat within a call. Intended use: allocate `side` with
+ *    spare rows beyond the trained entities and fold new users into them; als_recommend, als_rank_targets and
+ *    als_predict then work on those rows unchanged. The caller must not point dst_rows at rows a half in progress solves.
+ *  - At least one of host_out and dst_rows must be given.
+ *  - Every num_features whose factor stride is <= 128, in both precisions; wider: ALS_ERR_UNSUPPORTED.
+ *  - Checked on the host in O(n_queries + entries), ALS_ERR_INVALID_ARGUMENT naming the query: a decreasing q_ptr, an
+ *    index outside [0, opposite n_total_rows), a bad or repeated dst_rows entry. Opposite factors (or, with dst_rows,
+ *    `side`'s) not allocated/bound: ALS_ERR_STATE. n_queries == 0: ALS_OK, nothing touched.
+ *  - A query's result is bitwise repeatable and does not depend on the other queries of the call, on its position
+ *    in the call or on the launch shape: one workgroup owns one whole query and sums in one fixed order.
+ * Synchronous, on the engine's stream, after pending all-gathers. Reads the opposite side's plain factor table, never the
+ * pre-split copy, and uses als_recommend's grow-only workspace: a call between two chunks of one half leaves that half
+ * bitwise unchanged. */
+int als_fold_in(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
+                const int16_t* q_ratings, float lambda, const int64_t* dst_rows, void* host_out, int64_t out_ld);
+/* Launch shape als_fold_in would choose: info[0] = threads per workgroup, [1] = workgroups launched, [2] = entries staged
+ * per batch, [3] = dynamic LDS bytes per workgroup. */
+int als_fold_in_plan(const als_engine* e, int64_t n_queries, int64_t info[4]);
+
 /* Sum of (r - x_row . y_col)^2 over the block's observed ratings and their count (the RMSE/MSE
  * reduction of scripts/calculate_mse.py:78-90 computed on the device from the factors). Synchronous. */
 int als_sq_error(als_engine* e, int side, double* sum_sq_error, int64_t* count);
