@@ -19,6 +19,8 @@
 //            to; one barrier per column, the pivot column broadcast through LDS), forward and backward substitution
 //            with the vector in registers (one barrier per step). fp64 adds the one refinement step of
 //            als_solve_generic, the residual formed from the rows themselves.
+// KP is the engine's factor stride: 16, 32, 64 or 128, and in fp64 also 80, 96 and 112 (65..112 features are on the
+// generic solve path there, whose stride is the next multiple of 16).
 // DESIGN.md section 3.9 has the layout, the resource figures and the measurements.
 #include <climits>
 #include <type_traits>
@@ -331,8 +333,18 @@ hipError_t launch_kp(int kp, const FoldinArgs& a, const FoldinPlan& plan, hipStr
         case 32: return launch_one<T, 32>(a, plan, s);
         case 64: return launch_one<T, 64>(a, plan, s);
         case 128: return launch_one<T, 128>(a, plan, s);
-        default: return hipErrorInvalidValue;
+        default: break;
     }
+    // fp64 engines of 65..112 features are on the generic solve path, whose stride is the next multiple of 16
+    if constexpr (std::is_same<T, double>::value) {
+        switch (kp) {
+            case 80: return launch_one<T, 80>(a, plan, s);
+            case 96: return launch_one<T, 96>(a, plan, s);
+            case 112: return launch_one<T, 112>(a, plan, s);
+            default: break;
+        }
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace

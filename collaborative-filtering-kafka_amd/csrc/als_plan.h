@@ -229,7 +229,9 @@ constexpr int FOLDIN_TILE_PITCH = 17;
 constexpr int FOLDIN_TILE_ELEMS = 16 * FOLDIN_TILE_PITCH;
 constexpr int FOLDIN_MAX_WG_PER_CU = 8;
 constexpr int64_t FOLDIN_LDS_LIMIT = 160 * 1024;   // LDS of one gfx950 compute unit
-CFK_HOST_DEVICE constexpr int foldin_pitch(int kp) { return kp == 16 ? 16 : kp + 16; }
+// kp + 16 where kp is a multiple of 32, kp itself where it already is 16 mod 32 (16, and the strides 80 and 112 of fp64
+// engines on the generic solve path; 96 takes 112)
+CFK_HOST_DEVICE constexpr int foldin_pitch(int kp) { return kp % 32 == 16 ? kp : kp + 16; }
 CFK_HOST_DEVICE constexpr int foldin_tiles(int kp) { return (kp / 16) * (kp / 16 + 1) / 2; }
 CFK_HOST_DEVICE constexpr int64_t foldin_lds_bytes(int kp, int elem_bytes, int batch) {
     return (int64_t)elem_bytes *
@@ -242,7 +244,7 @@ struct FoldinPlan {
     int batch = 0;           // opposite rows staged per pass: a multiple of 4 (one MFMA step), at most FOLDIN_MAX_BATCH
     int64_t lds_bytes = 0;   // dynamic LDS of one workgroup
 };
-// Pure function of its arguments. kp: 16, 32, 64 or 128; elem_bytes: 4 or 8. The batch is the largest that fits the LDS
+// Pure function of its arguments. kp: 16, 32, 64 or 128, in fp64 also 80, 96 or 112; elem_bytes: 4 or 8. The batch is the largest that fits the LDS
 // beside the Gram (FOLDIN_MAX_BATCH for every supported shape); the grid is what the compute units hold at that LDS
 // size, at most FOLDIN_MAX_WG_PER_CU each. A query's result does not depend on the grid (one workgroup per query).
 FoldinPlan foldin_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count);

@@ -3,17 +3,21 @@
 // (tests/test_foldin_host.py). Sweeps every kp, both element sizes and n_queries from 1 to 10^7, checks every invariant
 // from the plan alone and prints one JSON line:
 // {"cases": n, "failed": {check: "count, first: shape"}, "plans": {"kp/elem/n_queries/cu": [threads, grid, batch, lds]}}.
+// With the argument `generic` it sweeps instead the strides only fp64 engines have (80, 96, 112: 65..112 features are on
+// the generic solve path there, whose stride is the next multiple of 16), at 8-byte elements.
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "als_plan.h"
 
-int main() {
-    const int kps[] = {16, 32, 64, 128};
-    const int elems[] = {4, 8};
+int main(int argc, char** argv) {
+    const bool generic = argc > 1 && !strcmp(argv[1], "generic");
+    const std::vector<int> kps = generic ? std::vector<int>{80, 96, 112} : std::vector<int>{16, 32, 64, 128};
+    const std::vector<int> elems = generic ? std::vector<int>{8} : std::vector<int>{4, 8};
     const int cus[] = {1, 8, 256};
     std::vector<int64_t> queries;
     for (int64_t n = 1; n <= 70; ++n) queries.push_back(n);

@@ -87,6 +87,74 @@ def anyk_bound(precision: str, k: int) -> float:
     return BOUND[precision]
 
 
+# The width ladder (test_gpu_foldin_edges.py), built for als_fold_in's batching: the last batch's tail is zero-filled up
+# to a whole 4-entry MFMA step (1..5), the 64-entry batch boundary from both sides (63..66, 127..130), a fourth and a
+# fifth batch (200, 257), the 16- and 32-entry neighbours, one empty query at the end; 512 opposite rows. WIDTH_KS: the
+# widths next to every factor stride (16 / 32 / 64 / 128) that the fold-in cases solve on it, at WIDTH_LAM.
+WIDTH_DEGS = (1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 66, 127, 128, 129, 130, 200, 257, 0)
+WIDTH_KS = {"f32": (1, 2, 3, 5, 15, 16, 17, 31, 33, 48, 63, 65, 96, 127), "f64": (1, 15, 16, 17, 33, 63, 65, 127)}
+# fp64 only: an fp64 engine of 65..112 features has the generic path's stride, the next multiple of 16 (65 above: 80);
+# these fill each of the strides 80, 96 and 112 and stop one feature into 96 and 112
+WIDTH_KS_F64_STRIDES = (80, 81, 96, 97, 112)
+WIDTH_LAM = 0.05
+# Repeated indices and the whole int16 rating range on that ladder: the widths, and the ratings drawn for the second
+REPEAT_KS = {"f32": (10, 16, 64, 128), "f64": (64,)}
+EXTREME_RATINGS = (-32768, -1, 0, 257, 32767)
+FOLDIN_BATCH = 64       # als_plan.h FOLDIN_MAX_BATCH: opposite rows staged per pass
+
+
+@functools.lru_cache(maxsize=None)
+def width_ladder() -> Ladder:
+    return ladder_block(WIDTH_DEGS, n_opp=512, seed=6)
+
+
+@functools.lru_cache(maxsize=None)
+def repeat_ladder(extreme: bool = False) -> Ladder:
+    """The width ladder with repeated indices: in every row of >= 2 entries the last index repeats the first, in rows
+    of >= 66 entries entry 64 also repeats entry 63 (a repeat across the 64-entry batch boundary). Every entry keeps
+    its own rating (1..5), or with `extreme` one drawn from EXTREME_RATINGS. No COO form."""
+    lad = width_ladder()
+    rp, col = lad.blk["row_ptr"], lad.blk["col"].copy()
+    for i, d in enumerate(lad.degs):
+        if d >= 2:
+            col[rp[i + 1] - 1] = col[rp[i]]
+        if d >= FOLDIN_BATCH + 2:
+            col[rp[i] + FOLDIN_BATCH] = col[rp[i] + FOLDIN_BATCH - 1]
+    rat = lad.blk["ratings"].copy()
+    if extreme:
+        rat = np.random.default_rng(9).choice(np.asarray(EXTREME_RATINGS), len(col)).astype(np.int16)
+    blk = {"row_ptr": rp.copy(), "col": col, "ratings": rat, "n_rows": len(lad.degs)}
+    side = oracle.Side(lad.side.ids.copy(), rp.copy(), col.copy(), rat.copy())
+    return Ladder(blk, side, None, lad.degs, lad.n_opp)
+
+
+def counted_once(side: oracle.Side) -> oracle.Side:
+    """Copy of `side` in which an index a row lists more than once counts once: every later occurrence is removed,
+    with its rating -- what a kernel computes that merges repeated indices instead of counting each."""
+    keep = np.ones(len(side.col), bool)
+    n = len(side.row_ptr) - 1
+    for i in range(n):
+        lo, hi = side.row_ptr[i], side.row_ptr[i + 1]
+        _, first = np.unique(side.col[lo:hi], return_index=True)
+        keep[lo:hi] = False
+        keep[lo + first] = True
+    rp = np.zeros_like(side.row_ptr)
+    np.cumsum([keep[side.row_ptr[i]:side.row_ptr[i + 1]].sum() for i in range(n)], out=rp[1:])
+    return oracle.Side(side.ids, rp, side.col[keep].copy(), side.ratings[keep].copy())
+
+
+@functools.lru_cache(maxsize=None)
+def width_inputs(k: int, entries: str = "distinct"):
+    """(ladder, factors, fp64 oracle, the reference's fp32 result) of a width-ladder case with k features at WIDTH_LAM;
+    entries: "distinct" (width_ladder), "repeat" or "extreme" (repeat_ladder). Computed once, read-only."""
+    lad = {"distinct": width_ladder, "repeat": repeat_ladder, "extreme": lambda: repeat_ladder(True)}[entries]()
+    F = factors(lad.n_opp, k)
+    ref64, ref32 = references(lad.side, F, WIDTH_LAM)
+    for a in (F, ref64, ref32):
+        a.setflags(write=False)
+    return lad, F, ref64, ref32
+
+
 BUCKETS = ((1, 1), (2, 32), (33, 64), (65, 128), (129, 330), (1023, 1 << 30))
 
 Ladder = namedtuple("Ladder", "blk side coo degs n_opp")

@@ -22,11 +22,11 @@ LDS_LIMIT = 160 * 1024
 
 def foldin_plan(kp: int, elem_bytes: int, n_queries: int, cu_count: int) -> dict:
     """foldin_plan of als_plan.cpp restated: the dynamic LDS is the Gram's lower-triangle tiles (16 rows of pitch 17),
-    `batch` staged rows of pitch kp + 16 (16 at kp = 16), four kp-vectors and the batch's ratings; the batch is the
-    largest multiple of 4 up to 64 that fits 160 KiB; the grid is what the compute units hold at that LDS size (at most
-    8 workgroups each), never more than the queries."""
+    `batch` staged rows of pitch kp + 16 (kp itself where that is 16 mod 32 already: 16, 80, 112), four kp-vectors and
+    the batch's ratings; the batch is the largest multiple of 4 up to 64 that fits 160 KiB; the grid is what the compute
+    units hold at that LDS size (at most 8 workgroups each), never more than the queries."""
     tiles = (kp // 16) * (kp // 16 + 1) // 2
-    pitch = 16 if kp == 16 else kp + 16
+    pitch = kp if kp % 32 == 16 else kp + 16
 
     def lds(batch):
         return elem_bytes * (tiles * 16 * 17 + batch * pitch + 4 * kp + batch)
@@ -53,7 +53,9 @@ def plan_sweep(tmp_path_factory):
         pytest.fail("no host compiler built foldin_plan_check with the sanitizers:\n" + "\n".join(errors))
     run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert run.returncode == 0 and run.stderr == "", run.stderr[-4000:]
-    return json.loads(run.stdout)
+    generic = subprocess.run([exe, "generic"], capture_output=True, text=True, timeout=120)
+    assert generic.returncode == 0 and generic.stderr == "", generic.stderr[-4000:]
+    return dict(json.loads(run.stdout), generic=json.loads(generic.stdout))
 
 
 def test_plan_sweep_holds_every_invariant(plan_sweep):
@@ -77,6 +79,21 @@ def test_python_restatement_equals_the_plan(plan_sweep):
     # the shapes DESIGN.md section 3.9 quotes
     assert foldin_plan(128, 8, 10 ** 7, 256) == {"threads": 256, "workgroups": 256, "batch": 64, "lds_bytes": 156672}
     assert foldin_plan(64, 4, 5000, 256) == {"threads": 256, "workgroups": 1280, "batch": 64, "lds_bytes": 32640}
+
+
+def test_plan_of_the_fp64_strides_between_64_and_128(plan_sweep):
+    """fp64 engines of 65..112 features are on the generic solve path, whose factor stride is the next multiple of 16:
+    80, 96 or 112. als_fold_in serves them too (als.h: every stride <= 128 in both precisions); the same invariants
+    hold for their plans, and the restatement equals them."""
+    g = plan_sweep["generic"]
+    n_queries = 70 + 6 * 3 + 14
+    assert g["cases"] == 3 * 3 * n_queries == len(g["plans"]) and g["failed"] == {}
+    for key, (threads, grid, batch, lds) in g["plans"].items():
+        kp, elem, nq, cu = (int(x) for x in key.split("/"))
+        assert elem == 8 and kp in (80, 96, 112) and batch == 64
+        assert foldin_plan(kp, elem, nq, cu) == {"threads": threads, "workgroups": grid, "batch": batch,
+                                                 "lds_bytes": lds}, key
+    assert foldin_plan(112, 8, 22, 256) == {"threads": 256, "workgroups": 22, "batch": 64, "lds_bytes": 122368}
 
 
 @pytest.mark.parametrize("world", [1, 2])

@@ -142,6 +142,111 @@ def test_anyk_reference_margin_and_mutant_margin(k, rows):
     assert nearest[i] >= rs.MARGIN * bound, (k, degs[i], nearest[i])
 
 
+WIDTH_KS = sorted(set(rs.WIDTH_KS["f32"]) | set(rs.WIDTH_KS["f64"]) | set(rs.WIDTH_KS_F64_STRIDES))
+REPEAT_KS = sorted(set(rs.REPEAT_KS["f32"]) | set(rs.REPEAT_KS["f64"]))
+
+
+def test_width_and_repeat_ladders_are_what_they_say():
+    lad, rep, ext = rs.width_ladder(), rs.repeat_ladder(), rs.repeat_ladder(True)
+    degs = lad.degs
+    assert degs.tolist() == list(rs.WIDTH_DEGS) and lad.n_opp == 512 and degs[-1] == 0 and (degs == 0).sum() == 1
+    b = rs.FOLDIN_BATCH
+    # the zero-filled tail of a 4-entry MFMA step, both sides of the first two batch boundaries, five batches
+    assert {1, 2, 3, 4, 5, b - 1, b, b + 1, b + 2, 2 * b - 1, 2 * b, 2 * b + 1, 2 * b + 2} <= set(degs.tolist())
+    assert -(-200 // b) == 4 and -(-257 // b) == 5
+    assert set(rs.WIDTH_KS["f64"]) <= set(rs.WIDTH_KS["f32"]) and max(WIDTH_KS) <= 128
+    for s in (16, 32, 64):                        # a width either side of every stride edge
+        assert {s - 1, s + 1} <= set(WIDTH_KS)
+    assert {1, 127} <= set(WIDTH_KS)
+    # fp64 engines above 64 features: every stride between 64 and 128 filled, and entered by one feature
+    assert {-(-k // 16) * 16 for k in rs.WIDTH_KS_F64_STRIDES + (65,)} == {80, 96, 112}
+    assert {80, 96, 112, 81, 97} <= set(rs.WIDTH_KS_F64_STRIDES)
+    rp = lad.blk["row_ptr"]
+    for other in (rep, ext):
+        assert np.array_equal(other.blk["row_ptr"], rp) and other.coo is None
+        assert np.array_equal(other.side.col, other.blk["col"]) and np.array_equal(other.side.ratings, other.blk["ratings"])
+        for i, d in enumerate(degs):
+            c, c0 = other.blk["col"][rp[i]:rp[i + 1]], lad.blk["col"][rp[i]:rp[i + 1]]
+            changed = np.nonzero(c != c0)[0].tolist()
+            assert changed == ([] if d < 2 else [d - 1] if d < b + 2 else [b, d - 1]), (i, d)
+            if d >= 2:
+                assert c[-1] == c[0]
+            if d >= b + 2:
+                assert c[b] == c[b - 1]
+            assert len(np.unique(c)) == d - len(changed)
+    assert np.array_equal(rep.blk["ratings"], lad.blk["ratings"])
+    # the extreme draw: every value of the int16 range's ends, 0 and a value beyond one byte; it holds a query whose
+    # ratings are all 0 (its solution is exactly zero): the one-entry row
+    r = ext.blk["ratings"]
+    assert r.dtype == np.int16 and set(r.tolist()) == set(rs.EXTREME_RATINGS)
+    all_zero = [int(d) for i, d in enumerate(degs) if d > 0 and not r[rp[i]:rp[i + 1]].any()]
+    assert all_zero == [1], all_zero
+    once = rs.counted_once(rep.side)
+    assert np.array_equal(np.diff(once.row_ptr), np.where(degs >= b + 2, degs - 2, np.where(degs >= 2, degs - 1, degs)))
+    same = rs.counted_once(lad.side)
+    assert np.array_equal(same.col, lad.side.col) and np.array_equal(same.row_ptr, lad.side.row_ptr)
+
+
+@pytest.mark.parametrize("k", WIDTH_KS)
+def test_width_ladder_reference_margin_and_mutant_margin(k):
+    """The yardstick of test_gpu_foldin_edges.py's width cases, settled with the oracle alone: on the width ladder, for
+    every width next to a stride edge, the reference's own fp32 arithmetic stays at or below BOUND / MARGIN on every
+    row and every one-entry mutant is at least MARGIN x BOUND away on every row of >= 2 entries. Measured: the
+    reference's worst row 1.2e-5 (k = 17, the one-entry row; every other width <= 7.2e-6) against the 2e-5 allowed;
+    the nearest mutant 9.6e-4 away (k = 1, the 128-entry row; every other width >= 4.2e-3) against the 5e-4 required."""
+    lad, F, ref64, ref32 = rs.width_inputs(k)
+    degs = lad.degs
+    bound = rs.BOUND["f32"]
+    rel32 = rs.row_errors(ref32, ref64)
+    worst = float(rel32[degs > 0].max())
+    print(f"k={k}: reference fp32 per-row max {worst:.3e} (row of {degs[rel32.argmax()]} entries)")
+    assert worst <= bound / rs.MARGIN
+    rs.check_rows(ref32, ref64, ref32, degs, "f32")
+    rs.check_rows(ref64, ref64, None, degs, "f64")
+    two = degs >= 2
+    nearest = np.full(len(degs), np.inf)
+    for name, mside in rs.mutants(lad.side).items():
+        mut = rs.oracle.update_side(mside, F, rs.WIDTH_LAM, "f64")
+        for precision in ("f32", "f64"):
+            bad = rs.rejected_rows(mut, ref64, degs, precision)
+            assert bad[two].all() and not bad[~two].any(), (name, precision, degs[two & ~bad][:8])
+        nearest = np.minimum(nearest, rs.row_errors(mut, ref64))
+    i = int(np.argmin(np.where(two, nearest, np.inf)))
+    print(f"k={k}: nearest mutant {nearest[i]:.2e} away (row of {degs[i]} entries)")
+    assert nearest[i] >= rs.MARGIN * bound, (k, degs[i], nearest[i])
+
+
+@pytest.mark.parametrize("k", REPEAT_KS)
+def test_repeated_index_counts_twice_and_counted_once_is_rejected(k):
+    """include/als.h: an index a query lists twice counts twice. On the repeat ladder the reference's own fp32
+    arithmetic stays at or below BOUND / MARGIN on every row, with ratings 1..5 (measured: <= 7.1e-6) and with the
+    extreme int16 ratings (<= 6.3e-6), and the "counted once" mutant -- the CSR with the repeats removed -- is
+    rejected on every row of >= 2 entries, MARGIN bounds away or more (measured: >= 3.0e-2)."""
+    for entries in ("repeat", "extreme"):
+        lad, F, ref64, ref32 = rs.width_inputs(k, entries)
+        worst = float(rs.row_errors(ref32, ref64)[lad.degs > 0].max())
+        print(f"k={k} {entries}: reference fp32 per-row max {worst:.3e}")
+        assert worst <= rs.BOUND["f32"] / rs.MARGIN
+        rs.check_rows(ref32, ref64, ref32, lad.degs, "f32")
+        rs.check_rows(ref64, ref64, None, lad.degs, "f64")
+    lad, F, ref64, ref32 = rs.width_inputs(k, "repeat")
+    degs = lad.degs
+    two = degs >= 2
+    mut = rs.oracle.update_side(rs.counted_once(lad.side), F, rs.WIDTH_LAM, "f64")
+    for precision in ("f32", "f64"):
+        bad = rs.rejected_rows(mut, ref64, degs, precision)
+        assert bad[two].all() and not bad[~two].any(), (precision, degs[two & ~bad][:8])
+    away = rs.row_errors(mut, ref64)
+    i = int(np.argmin(np.where(two, away, np.inf)))
+    print(f"k={k}: counted-once mutant {away[i]:.2e} away at the nearest (row of {degs[i]} entries)")
+    assert away[i] >= rs.MARGIN * rs.BOUND["f32"], (k, degs[i], away[i])
+    # an all-zero query of the extreme draw has an exactly zero solution, which row_errors then demands of the kernel
+    ext, _, ext64, _ = rs.width_inputs(k, "extreme")
+    rp, r = ext.blk["row_ptr"], ext.blk["ratings"]
+    zero_q = np.array([d > 0 and not r[rp[j]:rp[j + 1]].any() for j, d in enumerate(degs)])
+    assert zero_q.sum() >= 1 and not ext64[zero_q].any() and ext64[(degs > 0) & ~zero_q].any(axis=1).all()
+
+
 def test_comparator_rejects_other_damage(ladder):
     """Nonzero output on a row without a rating, a NaN, and a wrong shape are failures too; the report names the
     row, its degree and its task kind."""
