@@ -90,6 +90,10 @@ SIGNATURES = [
     ("als_rank_plan", _i, [_vp, _i64, _i64, _pi64]),
     ("als_fold_in", _i, [_vp, _i, _i64, _pi64, _pi32, _pi16, _f, _pi64, _vp, _i64]),
     ("als_fold_in_plan", _i, [_vp, _i64, _pi64]),
+    ("als_gram_table", _i, [_vp, _i, _vp, _i64]),
+    ("als_gram_table_plan", _i, [_vp, _i64, _pi64]),
+    ("als_solve_implicit", _i, [_vp, _i, _i64, _pi64, _pi32, _pi16, _f, _f, _pi64, _vp, _i64]),
+    ("als_solve_implicit_plan", _i, [_vp, _i64, _pi64]),
     ("als_sq_error", _i, [_vp, _i, _pd, _pi64]),
     ("als_synchronize", _i, [_vp]),
     ("als_integrity_status", _i, [_vp, ctypes.POINTER(ctypes.c_uint32), _i]),

@@ -21,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from .engine import ALSEngine, Dataset, SIDE_MOVIE, SIDE_USER
+from .engine import ALSEngine, Dataset, SIDE_MOVIE, SIDE_USER, SIDES
 
 
 def _table_digest(t: torch.Tensor) -> int:
@@ -407,6 +407,55 @@ class ALSApp:
         out = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
         return user_ids, out.astype(np.int64), score
 
+    # ---- implicit feedback (Hu, Koren, Volinsky 2008): single rank --------------------------------------------------
+    def _implicit_csr(self, side):
+        """The side's whole host CSR (row_ptr, col = opposite factor rows, int16 ratings), taken once and kept."""
+        if self.world > 1:
+            raise NotImplementedError("implicit-feedback training is single-rank: G = Y^T Y is additive over shards, "
+                                      "but the all-reduce of k x k per half is not built")
+        if not hasattr(self, "_implicit_blocks"):
+            self._implicit_blocks = [None, None]
+        if self._implicit_blocks[side] is None:
+            blk = self.ds.shard_block(side, 1, 0)
+            self._implicit_blocks[side] = (np.ascontiguousarray(blk["row_ptr"], np.int64),
+                                           np.ascontiguousarray(blk["col"], np.int32),
+                                           np.ascontiguousarray(blk["ratings"], np.int16),
+                                           int(blk["row_offset"]), int(blk["n_rows"]))
+        return self._implicit_blocks[side]
+
+    def implicit_half(self, side, alpha: float):
+        """One half of implicit-feedback ALS: every row of `side` from its ratings (confidence 1 + alpha r) and the
+        Gram of the whole opposite table, stored into the resident factors (ALSEngine.solve_implicit, this app's
+        lambda as the plain lambda of the model)."""
+        side = SIDES[side] if isinstance(side, str) else int(side)
+        row_ptr, col, rat, row_offset, n_rows = self._implicit_csr(side)
+        self.engine.solve_implicit(side, (row_ptr, col, rat), self.ALS_LAMBDA, alpha,
+                                   dst_rows=row_offset + np.arange(n_rows, dtype=np.int64), return_host=False)
+
+    def implicit_iteration(self, alpha: float):
+        self.implicit_half(SIDE_MOVIE, alpha)
+        self.implicit_half(SIDE_USER, alpha)
+
+    def implicit_loss(self, alpha: float) -> float:
+        """sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + lambda (|U|^2 + |M|^2) over the dense users x movies grid, c = 1 +
+        alpha r, p = [r > 0]. Host-side and fp64, for small data: the grid is materialised."""
+        row_ptr, col, rat, row_offset, n_rows = self._implicit_csr(SIDE_USER)
+        U = self.engine.read_factors(SIDE_USER, 0, self.info[SIDE_USER]["n_slots"]).astype(np.float64)
+        M = self.engine.read_factors(SIDE_MOVIE).astype(np.float64)
+        R = np.zeros((U.shape[0], M.shape[0]))
+        np.add.at(R, (row_offset + np.repeat(np.arange(n_rows), np.diff(row_ptr)), col), rat.astype(np.float64))
+        us, ms = self.ds.slots(SIDE_USER, 1), self.ds.slots(SIDE_MOVIE, 1)
+        U, M, R = U[us], M[ms], R[us][:, ms]
+        err = (R > 0).astype(np.float64) - U @ M.T
+        return float(np.sum((1.0 + alpha * R) * err * err) + self.ALS_LAMBDA * (np.sum(U * U) + np.sum(M * M)))
+
+    def fold_in_implicit(self, users, alpha: float, dst_rows=None) -> np.ndarray:
+        """fold_in() under the implicit-feedback model: the users' factors from ALSEngine.solve_implicit against the
+        resident movie factors."""
+        movie_rows = self.ds.slots(SIDE_MOVIE, self.world)
+        q_ptr, q_idx, q_rat, _, _, _ = foldin_queries(self.ds, self.world, movie_rows, users)
+        return self.engine.solve_implicit(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, alpha, dst_rows=dst_rows)
+
     def fold_in(self, users, dst_rows=None) -> np.ndarray:
         """User factors [n, k] of users that are not in the training data, from their (movie id, rating) lists and the
         resident movie factors (ALSEngine.fold_in with this app's lambda; foldin_queries maps the movie ids and skips
@@ -415,11 +464,13 @@ class ALSApp:
         q_ptr, q_idx, q_rat, _, _, _ = foldin_queries(self.ds, self.world, movie_rows, users)
         return self.engine.fold_in(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, dst_rows=dst_rows)
 
-    def recommend_for(self, users, top_n: int, exclude_seen: bool = True) -> tuple[np.ndarray, np.ndarray]:
+    def recommend_for(self, users, top_n: int, exclude_seen: bool = True,
+                      implicit_alpha: float | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Top-N movies for users that are not in the training data: their (movie id, rating) lists are folded into the
         spare rows of U (setup(spare_user_rows=...), as many users at a time as there are spare rows) and recommend()
         runs on those rows against all movies in ascending id. Returns (movie_ids [n, top_n], scores [n, top_n]) as
-        ALSApp.recommend does; exclude_seen leaves out the movies a user has rated."""
+        ALSApp.recommend does; exclude_seen leaves out the movies a user has rated. implicit_alpha: fold in under the
+        implicit-feedback model with that alpha (fold_in_implicit) instead of the explicit one."""
         if self.spare_user_rows < 1:
             raise ValueError("recommend_for needs spare user rows: setup(..., spare_user_rows=n)")
         movie_ids = self.ds.ids(SIDE_MOVIE)
@@ -432,7 +483,11 @@ class ALSApp:
             part = users[u0:u0 + self.spare_user_rows]
             q_ptr, q_idx, q_rat, excl_ptr, excl_idx, _ = foldin_queries(self.ds, self.world, movie_rows, part)
             rows = base + np.arange(len(part), dtype=np.int64)
-            self.engine.fold_in(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, dst_rows=rows, return_host=False)
+            if implicit_alpha is None:
+                self.engine.fold_in(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, dst_rows=rows, return_host=False)
+            else:
+                self.engine.solve_implicit(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, implicit_alpha,
+                                           dst_rows=rows, return_host=False)
             idx, sc = self.engine.recommend(rows, movie_rows, top_n, (excl_ptr, excl_idx) if exclude_seen else None)
             out[u0:u0 + len(part)] = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
             score[u0:u0 + len(part)] = sc

@@ -153,6 +153,21 @@ struct FoldinArgs {
     float lambda;
 };
 hipError_t launch_fold_in(int precision, int kp, const FoldinArgs& a, const FoldinPlan& plan, hipStream_t s);
+// Table Gram (als_implicit.hip): G = Y^T Y of table [n_rows][kp] into the dense symmetric gram [kp][kp] (both triangles,
+// padding zero), through `partial` (plan.partial_bytes): the slabs' tiles, summed in ascending slab order (fp32 in
+// double, rounded once). The geometry is gram_table_plan's; G does not depend on the device.
+hipError_t launch_gram_table(int precision, int kp, const void* table, int64_t n_rows, const GramTablePlan& plan,
+                             void* partial, void* gram, hipStream_t s);
+// Implicit-feedback solve (als_implicit.hip), arrays as in FoldinArgs: query q solves
+// x = (G + alpha sum_e r_e y_e y_e^T + lambda I)^-1 sum_{e: r_e > 0} (1 + alpha r_e) y_e, G the opposite table's Gram
+// from launch_gram_table. order[i] is the query the i-th step of the grid-stride loop takes (longest first).
+struct ImplicitArgs {
+    FoldinArgs f;             // lambda is the plain lambda of the model (not lambda n)
+    const void* gram;         // [kp][kp]
+    const int64_t* order;     // [n_queries]: a permutation of the queries
+    float alpha;
+};
+hipError_t launch_implicit(int precision, int kp, const ImplicitArgs& a, const FoldinPlan& plan, hipStream_t s);
 hipError_t launch_sq_error(int precision, int kp, const SqErrArgs& a, hipStream_t s);
 // Per-lane accumulator words (elements of the engine precision) of one partial slot: nacc * 64.
 int partial_words_per_lane(int precision, int kp, Path path);

@@ -438,4 +438,17 @@ FoldinPlan foldin_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count) 
     return p;
 }
 
+GramTablePlan gram_table_plan(int kp, int elem_bytes, int64_t n_rows, int cu_count) {
+    (void)cu_count;
+    GramTablePlan p;
+    n_rows = std::max<int64_t>(n_rows, 0);
+    const int64_t per = (n_rows + GRAM_TABLE_MAX_SLABS - 1) / GRAM_TABLE_MAX_SLABS;
+    p.rows_per_slab =
+        std::max<int64_t>(GRAM_TABLE_MIN_SLAB_ROWS, (per + FOLDIN_MAX_BATCH - 1) / FOLDIN_MAX_BATCH * FOLDIN_MAX_BATCH);
+    p.slabs = std::max<int64_t>(1, (n_rows + p.rows_per_slab - 1) / p.rows_per_slab);
+    p.lds_bytes = gram_table_lds_bytes(kp, elem_bytes);
+    p.partial_bytes = p.slabs * foldin_tiles(kp) * 256 * (int64_t)elem_bytes;
+    return p;
+}
+
 }  // namespace cfk

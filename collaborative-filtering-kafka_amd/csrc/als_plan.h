@@ -249,4 +249,29 @@ struct FoldinPlan {
 // size, at most FOLDIN_MAX_WG_PER_CU each. A query's result does not depend on the grid (one workgroup per query).
 FoldinPlan foldin_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count);
 
+// ---- implicit feedback: the table Gram and the implicit solve (als_implicit.hip) ------------------------------------
+// Table Gram G = Y^T Y of a whole factor table: slab s owns rows [s rows_per_slab, (s + 1) rows_per_slab) and one
+// FOLDIN_THREADS workgroup forms its lower-triangle tiles from batches of FOLDIN_MAX_BATCH rows staged at foldin_pitch;
+// a second kernel sums the slabs' tiles in ascending slab order. Slab count and length depend on n_rows alone (never on
+// the device), so G is bitwise the same everywhere: the length is GRAM_TABLE_MIN_SLAB_ROWS until that would need more
+// than GRAM_TABLE_MAX_SLABS slabs, then the smallest multiple of the batch that keeps the count within the cap.
+constexpr int64_t GRAM_TABLE_MAX_SLABS = 1024;
+constexpr int64_t GRAM_TABLE_MIN_SLAB_ROWS = 256;
+CFK_HOST_DEVICE constexpr int64_t gram_table_lds_bytes(int kp, int elem_bytes) {
+    return (int64_t)elem_bytes * ((int64_t)FOLDIN_MAX_BATCH * foldin_pitch(kp) + FOLDIN_MAX_BATCH);
+}
+struct GramTablePlan {
+    int threads = FOLDIN_THREADS;
+    int64_t slabs = 1;            // workgroups of the first kernel, at most GRAM_TABLE_MAX_SLABS
+    int64_t rows_per_slab = 0;    // a multiple of FOLDIN_MAX_BATCH; the last slab may be short
+    int64_t lds_bytes = 0;        // dynamic LDS of one workgroup: one staged batch
+    int64_t partial_bytes = 0;    // workspace of the slabs' tiles: slabs x foldin_tiles(kp) x 256 elements
+};
+// Pure function of kp, elem_bytes and n_rows; cu_count is accepted and ignored (the plan must not depend on the device).
+GramTablePlan gram_table_plan(int kp, int elem_bytes, int64_t n_rows, int cu_count);
+// The implicit solve has fold-in's launch contract and LDS layout: its plan is foldin_plan's.
+inline FoldinPlan implicit_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count) {
+    return foldin_plan(kp, elem_bytes, n_queries, cu_count);
+}
+
 }  // namespace cfk

@@ -28,6 +28,31 @@ def _side(s) -> int:
     return SIDES[s] if isinstance(s, str) else int(s)
 
 
+def _query_arrays(queries, dst_rows):
+    """(n, ptr, idx, ratings, dst_rows) of a fold_in / solve_implicit call as contiguous arrays of the ABI's types, with
+    valid pointers for empty lists."""
+    qp = np.ascontiguousarray(queries[0], np.int64)
+    qi = np.ascontiguousarray(queries[1], np.int32)
+    qr = np.ascontiguousarray(queries[2], np.int16)
+    if qp.ndim != 1 or len(qp) < 1:
+        raise ValueError("queries: ptr must have n + 1 entries")
+    n = len(qp) - 1
+    if len(qi) != len(qr):
+        raise ValueError("queries: idx and ratings must have the same length")
+    if int(qp[-1]) > len(qi) or int(qp[0]) < 0:
+        raise ValueError("queries: ptr points outside idx")
+    if qi.size == 0:
+        qi, qr = np.zeros(1, np.int32), np.zeros(1, np.int16)   # valid pointers for empty lists
+    dr = None
+    if dst_rows is not None:
+        dr = np.ascontiguousarray(dst_rows, np.int64)
+        if len(dr) != n:
+            raise ValueError("dst_rows must have one entry per query")
+        if dr.size == 0:
+            dr = np.zeros(1, np.int64)
+    return n, qp, qi, qr, dr
+
+
 def factor_stride(k: int, precision: str = "f32") -> int:
     """Padded factor-row stride of an engine (als_factor_stride): 16 / 32 / 64 / 128 on the wave-per-row kernels,
     the next multiple of 16 on the generic path (fp32 k > 128, fp64 k > 64)."""
@@ -488,25 +513,7 @@ class ALSEngine:
         the order given. Returns the [n, k] solutions x = (Y^T Y + lam n I)^-1 Y^T r (zeros for a query without
         entries) in the engine's precision, or None with return_host=False. dst_rows: factor rows of `side` that also
         receive the results on the device (bitwise the returned rows), e.g. spare rows after the trained entities."""
-        qp = np.ascontiguousarray(queries[0], np.int64)
-        qi = np.ascontiguousarray(queries[1], np.int32)
-        qr = np.ascontiguousarray(queries[2], np.int16)
-        if qp.ndim != 1 or len(qp) < 1:
-            raise ValueError("queries: ptr must have n + 1 entries")
-        n = len(qp) - 1
-        if len(qi) != len(qr):
-            raise ValueError("queries: idx and ratings must have the same length")
-        if int(qp[-1]) > len(qi) or int(qp[0]) < 0:
-            raise ValueError("queries: ptr points outside idx")
-        if qi.size == 0:
-            qi, qr = np.zeros(1, np.int32), np.zeros(1, np.int16)   # valid pointers for empty lists
-        dr = None
-        if dst_rows is not None:
-            dr = np.ascontiguousarray(dst_rows, np.int64)
-            if len(dr) != n:
-                raise ValueError("dst_rows must have one entry per query")
-            if dr.size == 0:
-                dr = np.zeros(1, np.int64)
+        n, qp, qi, qr, dr = _query_arrays(queries, dst_rows)
         out = np.zeros((n, self.k), self.np_dtype) if return_host else None
         call("als_fold_in", self._h, _side(side), n, ptr(qp, ctypes.c_int64), ptr(qi, ctypes.c_int32),
              ptr(qr, ctypes.c_int16), float(np.float32(lam)), ptr(dr, ctypes.c_int64) if dr is not None else None,
@@ -517,6 +524,39 @@ class ALSEngine:
         """Launch shape fold_in() would choose (als_fold_in_plan)."""
         v = (ctypes.c_int64 * 4)()
         call("als_fold_in_plan", self._h, int(n_queries), v)
+        return {"threads": v[0], "workgroups": v[1], "batch": v[2], "lds_bytes": v[3]}
+
+    def gram_table(self, side) -> np.ndarray:
+        """Y^T Y [k, k] of `side`'s resident factor table in the engine's precision (als_gram_table): exactly symmetric,
+        bitwise repeatable, the same on every device. What solve_implicit() computes for the opposite side."""
+        out = np.zeros((self.k, self.k), self.np_dtype)
+        call("als_gram_table", self._h, _side(side), out.ctypes.data_as(ctypes.c_void_p), self.k)
+        return out
+
+    def gram_table_plan(self, n_rows: int) -> dict:
+        """Launch shape gram_table() would choose for a table of n_rows rows (als_gram_table_plan)."""
+        v = (ctypes.c_int64 * 4)()
+        call("als_gram_table_plan", self._h, int(n_rows), v)
+        return {"threads": v[0], "slabs": v[1], "rows_per_slab": v[2], "lds_bytes": v[3]}
+
+    def solve_implicit(self, side, queries, lam: float, alpha: float, dst_rows=None,
+                       return_host: bool = True) -> np.ndarray | None:
+        """Implicit-feedback factor rows (als_solve_implicit; Hu, Koren, Volinsky 2008). queries and dst_rows as in
+        fold_in(); ratings >= 0. Returns the [n, k] solutions x = (G + alpha sum r y y^T + lam I)^-1 sum_{r > 0}
+        (1 + alpha r) y, G = Y^T Y of the whole opposite table (zeros for a query without entries), or None with
+        return_host=False."""
+        n, qp, qi, qr, dr = _query_arrays(queries, dst_rows)
+        out = np.zeros((n, self.k), self.np_dtype) if return_host else None
+        call("als_solve_implicit", self._h, _side(side), n, ptr(qp, ctypes.c_int64), ptr(qi, ctypes.c_int32),
+             ptr(qr, ctypes.c_int16), float(np.float32(lam)), float(np.float32(alpha)),
+             ptr(dr, ctypes.c_int64) if dr is not None else None,
+             out.ctypes.data_as(ctypes.c_void_p) if out is not None else None, self.k)
+        return out
+
+    def solve_implicit_plan(self, n_queries: int) -> dict:
+        """Launch shape solve_implicit() would choose (als_solve_implicit_plan)."""
+        v = (ctypes.c_int64 * 4)()
+        call("als_solve_implicit_plan", self._h, int(n_queries), v)
         return {"threads": v[0], "workgroups": v[1], "batch": v[2], "lds_bytes": v[3]}
 
     def sq_error(self, side="movie"):

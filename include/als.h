@@ -261,6 +261,50 @@ int als_fold_in(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr
  * per batch, [3] = dynamic LDS bytes per workgroup. */
 int als_fold_in_plan(const als_engine* e, int64_t n_queries, int64_t info[4]);
 
+/* Implicit-feedback ALS (Hu, Koren, Volinsky 2008; no reference counterpart: the reference trains on explicit ratings
+ * only). Every unobserved pair counts as a weak negative, so a query's system holds the Gram of the whole opposite table:
+ *     G = Y^T Y                                      (k x k, all n_total_rows rows of the opposite side's matrix)
+ *     A = G + alpha sum_e r_e y_e y_e^T + lambda I   (plain lambda, as in the paper: not lambda n)
+ *     b = sum_{e: r_e > 0} (1 + alpha r_e) y_e
+ *     x = A^-1 b
+ * over the query's entries (i_e, r_e): confidence c = 1 + alpha r, preference p = [r > 0].
+ *
+ * als_gram_table: Y^T Y of `side`'s own resident table, its k x k leading block to host_out (float for ALS_F32, double
+ * for ALS_F64; row stride out_ld >= num_features elements). Row slabs whose count and length depend on the row count
+ * alone are multiplied on the matrix pipe at full input precision and summed in ascending slab order (fp32 in double,
+ * rounded once), so G is exactly symmetric, bitwise repeatable and the same on every device. Synchronous and diagnostic:
+ * it is what als_solve_implicit computes for the opposite side on every call. Factors of `side` not allocated/bound:
+ * ALS_ERR_STATE. Factor stride > 128: ALS_ERR_UNSUPPORTED. Uses als_recommend's grow-only workspace. */
+int als_gram_table(als_engine* e, int side, void* host_out, int64_t out_ld);
+/* Launch shape als_gram_table would choose for a table of n_rows rows: info[0] = threads per workgroup, [1] = slabs
+ * (at most 1024), [2] = rows per slab, [3] = dynamic LDS bytes per workgroup. */
+int als_gram_table_plan(const als_engine* e, int64_t n_rows, int64_t info[4]);
+/* als_solve_implicit: the factor rows x of the model above, for ad-hoc queries or for a whole training half.
+ *  - side, n_queries, q_ptr, q_idx, q_ratings, dst_rows, host_out, out_ld: exactly as in als_fold_in (entries used in the
+ *    order given, q_ptr[0] != 0 rebased, fewer than 2^31 entries, at least one of host_out and dst_rows, dst_rows bit for
+ *    bit the host result with the columns >= num_features zero, no other row and never the sentinel touched).
+ *    dst_rows names rows of `side`; the Gram is the OPPOSITE side's, so a call never writes the table it sums.
+ *  - Ratings are >= 0; a negative one is ALS_ERR_INVALID_ARGUMENT naming the query. r_e = 0 is allowed and contributes
+ *    nothing: the result is bit for bit that of the query without the entry. A repeated index counts twice.
+ *  - A query without entries gives the zero vector, written directly with no solve.
+ *  - lambda > 0 and alpha > 0, both finite; anything else is ALS_ERR_INVALID_ARGUMENT.
+ *  - G of the opposite table is recomputed on every call (als_gram_table's kernels): the engine keeps no state that a
+ *    later change of the factors could leave stale.
+ *  - Checked on the host in O(n_queries + entries), ALS_ERR_INVALID_ARGUMENT naming the query: a decreasing q_ptr, an
+ *    index outside [0, opposite n_total_rows), a bad or repeated dst_rows entry, a negative rating. Factor stride > 128:
+ *    ALS_ERR_UNSUPPORTED. Opposite factors (or, with dst_rows, `side`'s) not allocated/bound: ALS_ERR_STATE.
+ *    n_queries == 0: ALS_OK, nothing touched.
+ *  - A query's result is bitwise repeatable and depends on its own entries, G, lambda and alpha only: not on the other
+ *    queries, its position in the call or the launch shape (one workgroup owns one whole query and sums in one fixed
+ *    order; the workgroups take the queries longest first).
+ * Synchronous, on the engine's stream, after pending all-gathers. Reads the plain factor tables and uses als_recommend's
+ * grow-only workspace only: a call between two chunks of an explicit half leaves that half bitwise unchanged. */
+int als_solve_implicit(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
+                       const int16_t* q_ratings, float lambda, float alpha, const int64_t* dst_rows, void* host_out,
+                       int64_t out_ld);
+/* Launch shape als_solve_implicit would choose: info[] as in als_fold_in_plan. */
+int als_solve_implicit_plan(const als_engine* e, int64_t n_queries, int64_t info[4]);
+
 /* Sum of (r - x_row . y_col)^2 over the block's observed ratings and their count (the RMSE/MSE
  * reduction of scripts/calculate_mse.py:78-90 computed on the device from the factors). Synchronous. */
 int als_sq_error(als_engine* e, int side, double* sum_sq_error, int64_t* count);
