@@ -1,7 +1,8 @@
 // als_engine_impl.h -- the engine's state and the helpers its translation units share: als_engine.cpp (lifetime,
 // environment, streams, synchronisation, timing, introspection), als_engine_block.cpp (block upload, chunks, row
-// layout), als_engine_solve.cpp (factors, the half-iteration launch, squared error, predict, recommend) and
-// als_engine_comm.cpp (the RCCL exchange). Private to csrc/.
+// layout), als_engine_solve.cpp (factors, the half-iteration launch, squared error, predict, recommend, held-out
+// ranks), als_engine_query.cpp (fold-in, the implicit solve, the table Gram) and als_engine_comm.cpp (the RCCL
+// exchange). Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -186,5 +187,8 @@ int stream_wait(als_engine* e, hipStream_t s);
 // found a slot it could not see freshly written by this launch's PARTIAL task makes every later synchronising
 // call fail until als_integrity_status(..., reset = 1).
 int sync_checked(als_engine* e);
+// Make sure the pinned staging buffer (h_stage) of the factor I/O and the query read-back exists
+// (als_engine_solve.cpp).
+int ensure_stage(als_engine* e);
 
 }  // namespace cfk_detail

@@ -1,0 +1,302 @@
+// als_engine_query.cpp -- the calls that solve ad-hoc queries against the resident factors: als_fold_in (the explicit
+// normal equation) and als_solve_implicit (implicit feedback) over one host path, solve_queries, with als_gram_table
+// and the three *_plan calls. All of them are synchronous, keep no per-engine state and work in d_rec, the grow-only
+// workspace of als_recommend / als_rank_targets: none of those calls is reading it when another starts.
+#include "als_engine_impl.h"
+
+#include <cmath>
+#include <unordered_set>
+
+using namespace cfk_detail;
+
+namespace {
+
+int check_stride(const als_engine* e, const char* fn) {
+    if (e->kp > cfk::FOLDIN_MAX_KP)
+        return fail(ALS_ERR_UNSUPPORTED, "%s: factor stride %d exceeds the supported %d", fn, e->kp, cfk::FOLDIN_MAX_KP);
+    return ALS_OK;
+}
+
+// What the *_plan calls check: `fn` is the call the plan is of, `count` the name of its count argument.
+int check_plan_call(const als_engine* e, const int64_t* info, const char* fn, const char* count, int64_t n) {
+    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (n < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s_plan: %s < 0", fn, count);
+    return check_stride(e, fn);
+}
+
+int plan_info(int64_t info[4], int64_t threads, int64_t groups, int64_t per_group, int64_t lds_bytes) {
+    info[0] = threads;
+    info[1] = groups;
+    info[2] = per_group;
+    info[3] = lds_bytes;
+    return ALS_OK;
+}
+
+// The query CSR and destination rows of als_fold_in / als_solve_implicit, checked in O(n_queries + entries); every
+// message names the query. *nnz_out = the entry count (below 2^31).
+int check_queries(const char* fn, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx, const int64_t* dst_rows,
+                  const Factors& self, const Factors& opp, int64_t* nnz_out) {
+    const int64_t p0 = q_ptr[0];
+    if (p0 < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr[0] is negative", fn);
+    for (int64_t q = 0; q < n_queries; ++q)
+        if (q_ptr[q + 1] < q_ptr[q])
+            return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr decreases at query %lld", fn, (long long)q);
+    const int64_t nnz = q_ptr[n_queries] - p0;
+    if (nnz > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: the number of entries must be below 2^31", fn);
+    for (int64_t q = 0; q < n_queries; ++q)
+        for (int64_t x = q_ptr[q]; x < q_ptr[q + 1]; ++x)
+            if (q_idx[x] < 0 || q_idx[x] >= opp.n_rows)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: index %d of query %lld is outside [0, %lld)", fn, (int)q_idx[x],
+                            (long long)q, (long long)opp.n_rows);
+    if (dst_rows) {
+        std::unordered_set<int64_t> seen;
+        seen.reserve((size_t)n_queries * 2);
+        for (int64_t q = 0; q < n_queries; ++q) {
+            if (dst_rows[q] < 0 || dst_rows[q] >= self.n_rows)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows[%lld] = %lld of query %lld is outside [0, %lld)", fn,
+                            (long long)q, (long long)dst_rows[q], (long long)q, (long long)self.n_rows);
+            if (!seen.insert(dst_rows[q]).second)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows repeats row %lld at query %lld", fn,
+                            (long long)dst_rows[q], (long long)q);
+        }
+    }
+    *nnz_out = nnz;
+    return ALS_OK;
+}
+
+// The first k columns of the nr kp-wide rows in the pinned staging buffer to host_out (row stride out_ld elements).
+void unpack_stage(const als_engine* e, int64_t nr, void* host_out, int64_t out_ld) {
+    const size_t es = e->elem(), row_bytes = (size_t)e->kp * es;
+    const char* stage = (const char*)e->h_stage.get();
+    for (int64_t i = 0; i < nr; ++i)
+        std::memcpy((char*)host_out + (size_t)i * out_ld * es, stage + i * row_bytes, (size_t)e->k * es);
+}
+
+// The first k columns of n kp-wide device rows to host_out, through the pinned staging buffer in as many passes as it
+// takes, the way als_read_factors reads. Waits for the stream.
+int download_rows(als_engine* e, const char* fn, const char* d_rows, int64_t n, void* host_out, int64_t out_ld) {
+    if (int r = ensure_stage(e)) return r;
+    const size_t es = e->elem(), row_bytes = (size_t)e->kp * es;
+    const int64_t rows_per = (int64_t)(e->h_stage.bytes() / row_bytes);
+    for (int64_t r = 0; r < n; r += rows_per) {
+        const int64_t nr = std::min(rows_per, n - r);
+        hipError_t st = cfk::launch_download(d_rows + (size_t)r * row_bytes, e->h_stage.get(), (size_t)nr * row_bytes, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(st));
+        unpack_stage(e, nr, (char*)host_out + (size_t)r * out_ld * es, out_ld);
+    }
+    return ALS_OK;
+}
+
+// One call of als_fold_in or als_solve_implicit.
+struct QueryCall {
+    const char* fn;
+    int side;
+    int64_t n_queries;
+    const int64_t* q_ptr;
+    const int32_t* q_idx;
+    const int16_t* q_ratings;
+    float lambda;
+    const float* alpha;   // NULL: the explicit model (lambda n, any lambda >= 0); else the implicit one
+    const int64_t* dst_rows;
+    void* host_out;
+    int64_t out_ld;
+};
+
+int solve_queries(als_engine* e, const QueryCall& c) {
+    const char* fn = c.fn;
+    const bool implicit = c.alpha != nullptr;
+    const int64_t n_queries = c.n_queries;
+    if (int r = check_engine(e)) return r;
+    if (int r = check_side(c.side)) return r;
+    if (n_queries < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: n_queries < 0", fn);
+    if (int r = check_stride(e, fn)) return r;
+    const Factors& self = e->fac[c.side];
+    const Factors& opp = e->fac[1 - c.side];
+    if (!opp.ptr) return fail(ALS_ERR_STATE, "%s: factors of side %d (the opposite side) not allocated/bound", fn, 1 - c.side);
+    if (c.dst_rows && !self.ptr)
+        return fail(ALS_ERR_STATE, "%s: dst_rows given but factors of side %d not allocated/bound", fn, c.side);
+    if (implicit) {
+        if (!(c.lambda > 0.f) || !std::isfinite(c.lambda))
+            return fail(ALS_ERR_INVALID_ARGUMENT, "%s: lambda must be positive and finite", fn);
+        if (!(*c.alpha > 0.f) || !std::isfinite(*c.alpha))
+            return fail(ALS_ERR_INVALID_ARGUMENT, "%s: alpha must be positive and finite", fn);
+    }
+    if (n_queries == 0) return ALS_OK;
+    if (!c.q_ptr || !c.q_idx || !c.q_ratings)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr, q_idx and q_ratings must be given", fn);
+    if (!c.dst_rows && !c.host_out) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows and host_out are both NULL", fn);
+    if (c.host_out && c.out_ld < e->k)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "%s: out_ld (%lld) < num_features (%d)", fn, (long long)c.out_ld, e->k);
+    if (!implicit && !(c.lambda >= 0.f)) return fail(ALS_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
+    int64_t nnz = 0;
+    if (int r = check_queries(fn, n_queries, c.q_ptr, c.q_idx, c.dst_rows, self, opp, &nnz)) return r;
+    const int64_t p0 = c.q_ptr[0];
+    if (implicit)
+        for (int64_t q = 0; q < n_queries; ++q)
+            for (int64_t x = c.q_ptr[q]; x < c.q_ptr[q + 1]; ++x)
+                if (c.q_ratings[x] < 0)
+                    return fail(ALS_ERR_INVALID_ARGUMENT, "%s: rating %d of query %lld is negative", fn, (int)c.q_ratings[x],
+                                (long long)q);
+    const cfk::FoldinPlan p = implicit ? cfk::implicit_plan(e->kp, (int)e->elem(), n_queries, e->cu_count)
+                                       : cfk::foldin_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
+    if (p.lds_bytes > cfk::FOLDIN_LDS_LIMIT) return fail(ALS_ERR_UNSUPPORTED, "%s: launch plan exceeds the LDS", fn);
+    cfk::GramTablePlan gp;
+    if (implicit) gp = cfk::gram_table_plan(e->kp, (int)e->elem(), opp.n_rows, e->cu_count);
+    // the device ranges index the uploaded slice: rebased to 0. Implicit: the order the workgroups take the queries in,
+    // longest first (stable), so that the one long query of a training half starts first instead of last. Results do
+    // not depend on it.
+    std::vector<int64_t> ptr0, order;
+    const int64_t* ptr = c.q_ptr;
+    if (p0 != 0) {
+        ptr0.resize(n_queries + 1);
+        for (int64_t q = 0; q <= n_queries; ++q) ptr0[q] = ptr[q] - p0;
+        ptr = ptr0.data();
+    }
+    if (implicit) {
+        order.resize(n_queries);
+        for (int64_t q = 0; q < n_queries; ++q) order[q] = q;
+        std::stable_sort(order.begin(), order.end(),
+                         [&](int64_t x, int64_t y) { return ptr[x + 1] - ptr[x] > ptr[y + 1] - ptr[y]; });
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (int r = wait_gathers(e, true, true)) return r;
+    // workspace, every part 256-byte aligned: ranges, order, indices, ratings, destination rows, the opposite table's
+    // Gram and its slabs' tiles, the kp-wide result rows
+    const size_t row_bytes = (size_t)e->kp * e->elem();
+    int64_t need = 0;
+    auto part = [&need](bool used, int64_t bytes) {
+        const int64_t off = need;
+        if (used) need += (bytes + 255) / 256 * 256;
+        return off;
+    };
+    const int64_t off_ptr = part(true, (n_queries + 1) * 8);
+    const int64_t off_ord = part(implicit, n_queries * 8);
+    const int64_t off_idx = part(true, nnz * 4);
+    const int64_t off_rat = part(true, nnz * 2);
+    const int64_t off_dst = part(c.dst_rows != nullptr, n_queries * 8);
+    const int64_t off_gram = part(implicit, (int64_t)e->kp * (int64_t)row_bytes);
+    const int64_t off_part = part(implicit, gp.partial_bytes);
+    const int64_t off_out = part(true, n_queries * (int64_t)row_bytes);
+    if ((size_t)need > e->d_rec.size()) {   // grow-only; the stream may still be reading the old one
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const hipError_t st = e->d_rec.reserve((size_t)need);
+        if (st != hipSuccess)
+            return fail(ALS_ERR_OUT_OF_MEMORY, "%s: device allocation (%zu bytes): %s", fn, (size_t)need, hipGetErrorString(st));
+    }
+    // a result that fits the pinned staging buffer is queued behind the kernel, so the call waits for the stream once
+    bool one_pass = false;
+    if (c.host_out) {
+        if (int r = ensure_stage(e)) return r;
+        one_pass = n_queries <= (int64_t)(e->h_stage.bytes() / row_bytes);
+    }
+    char* w = e->d_rec.get();
+    cfk::ImplicitArgs a{};
+    a.f.opp = opp.ptr;
+    a.f.self = self.ptr;
+    a.f.out = w + off_out;
+    a.f.q_ptr = (const int64_t*)(w + off_ptr);
+    a.f.q_idx = (const int32_t*)(w + off_idx);
+    a.f.q_rat = (const int16_t*)(w + off_rat);
+    a.f.dst_rows = c.dst_rows ? (const int64_t*)(w + off_dst) : nullptr;
+    a.f.n_queries = n_queries;
+    a.f.k = e->k;
+    a.f.lambda = c.lambda;
+    hipError_t st = hipMemcpyAsync(w + off_ptr, ptr, (n_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && nnz > 0)
+        st = hipMemcpyAsync(w + off_idx, c.q_idx + p0, nnz * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && nnz > 0)
+        st = hipMemcpyAsync(w + off_rat, c.q_ratings + p0, nnz * sizeof(int16_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess && c.dst_rows)
+        st = hipMemcpyAsync(w + off_dst, c.dst_rows, n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    if (implicit) {
+        a.gram = w + off_gram;
+        a.order = (const int64_t*)(w + off_ord);
+        a.alpha = *c.alpha;
+        if (st == hipSuccess)
+            st = hipMemcpyAsync(w + off_ord, order.data(), n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+        // G of the opposite table, recomputed on every call: no per-engine state that could go stale
+        if (st == hipSuccess)
+            st = cfk::launch_gram_table(e->precision, e->kp, opp.ptr, opp.n_rows, gp, w + off_part, w + off_gram, e->stream);
+        if (st == hipSuccess) st = cfk::launch_implicit(e->precision, e->kp, a, p, e->stream);
+    } else if (st == hipSuccess) {
+        st = cfk::launch_fold_in(e->precision, e->kp, a.f, p, e->stream);
+    }
+    if (st == hipSuccess && one_pass)
+        st = cfk::launch_download(w + off_out, e->h_stage.get(), (size_t)n_queries * row_bytes, e->stream);
+    // the host arrays are pageable: the stream has to pass the copies before this call returns
+    const hipError_t st2 = hipStreamSynchronize(e->stream);
+    if (st == hipSuccess) st = st2;
+    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(st));
+    if (one_pass) {
+        unpack_stage(e, n_queries, c.host_out, c.out_ld);
+    } else if (c.host_out) {
+        if (int r = download_rows(e, fn, w + off_out, n_queries, c.host_out, c.out_ld)) return r;
+    }
+    return sync_checked(e);
+}
+
+}  // namespace
+
+extern "C" {
+
+int als_fold_in_plan(const als_engine* e, int64_t n_queries, int64_t info[4]) {
+    if (int r = check_plan_call(e, info, "als_fold_in", "n_queries", n_queries)) return r;
+    const cfk::FoldinPlan p = cfk::foldin_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
+    return plan_info(info, p.threads, p.grid, p.batch, p.lds_bytes);
+}
+
+int als_fold_in(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
+                const int16_t* q_ratings, float lambda, const int64_t* dst_rows, void* host_out, int64_t out_ld) {
+    return solve_queries(e, {"als_fold_in", side, n_queries, q_ptr, q_idx, q_ratings, lambda, nullptr, dst_rows, host_out,
+                             out_ld});
+}
+
+int als_gram_table_plan(const als_engine* e, int64_t n_rows, int64_t info[4]) {
+    if (int r = check_plan_call(e, info, "als_gram_table", "n_rows", n_rows)) return r;
+    const cfk::GramTablePlan p = cfk::gram_table_plan(e->kp, (int)e->elem(), n_rows, e->cu_count);
+    return plan_info(info, p.threads, p.slabs, p.rows_per_slab, p.lds_bytes);
+}
+
+int als_gram_table(als_engine* e, int side, void* host_out, int64_t out_ld) {
+    if (int r = check_engine(e)) return r;
+    if (int r = check_side(side)) return r;
+    if (int r = check_stride(e, "als_gram_table")) return r;
+    const Factors& tab = e->fac[side];
+    if (!tab.ptr) return fail(ALS_ERR_STATE, "als_gram_table: factors of side %d not allocated/bound", side);
+    if (!host_out) return fail(ALS_ERR_INVALID_ARGUMENT, "als_gram_table: host_out is NULL");
+    if (out_ld < e->k)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_gram_table: out_ld (%lld) < num_features (%d)", (long long)out_ld, e->k);
+    const cfk::GramTablePlan p = cfk::gram_table_plan(e->kp, (int)e->elem(), tab.n_rows, e->cu_count);
+    HIP_TRY(hipSetDevice(e->device));
+    if (int r = wait_gathers(e, true, true)) return r;
+    // workspace: the kp x kp result, then the slabs' tiles
+    const size_t gram_bytes = ((size_t)e->kp * e->kp * e->elem() + 255) / 256 * 256;
+    const size_t need = gram_bytes + (size_t)p.partial_bytes;
+    if (need > e->d_rec.size()) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const hipError_t st = e->d_rec.reserve(need);
+        if (st != hipSuccess)
+            return fail(ALS_ERR_OUT_OF_MEMORY, "als_gram_table: device allocation (%zu bytes): %s", need, hipGetErrorString(st));
+    }
+    char* w = e->d_rec.get();
+    const hipError_t st = cfk::launch_gram_table(e->precision, e->kp, tab.ptr, tab.n_rows, p, w + gram_bytes, w, e->stream);
+    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_gram_table: %s", hipGetErrorString(st));
+    if (int r = download_rows(e, "als_gram_table", w, e->k, host_out, out_ld)) return r;
+    return sync_checked(e);
+}
+
+int als_solve_implicit_plan(const als_engine* e, int64_t n_queries, int64_t info[4]) {
+    if (int r = check_plan_call(e, info, "als_solve_implicit", "n_queries", n_queries)) return r;
+    const cfk::FoldinPlan p = cfk::implicit_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
+    return plan_info(info, p.threads, p.grid, p.batch, p.lds_bytes);
+}
+
+int als_solve_implicit(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
+                       const int16_t* q_ratings, float lambda, float alpha, const int64_t* dst_rows, void* host_out,
+                       int64_t out_ld) {
+    return solve_queries(e, {"als_solve_implicit", side, n_queries, q_ptr, q_idx, q_ratings, lambda, &alpha, dst_rows,
+                             host_out, out_ld});
+}
+
+}  // extern "C"

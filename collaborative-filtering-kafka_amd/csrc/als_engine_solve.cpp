@@ -1,12 +1,19 @@
 // als_engine_solve.cpp -- what runs on the resident factors: factor buffers and their I/O, the half-iteration launch,
-// squared error, predict, recommend, held-out ranks and fold-in. The steady-state half (launch_half) allocates nothing and creates no stream
-// or event: the side stream and its two events are made by the first half that needs them, timing events come from
-// the engine's pool.
+// squared error, predict, recommend and held-out ranks (the calls that solve ad-hoc queries are in
+// als_engine_query.cpp). The steady-state half (launch_half) allocates nothing and creates no stream or event: the side
+// stream and its two events are made by the first half that needs them, timing events come from the engine's pool.
 #include "als_engine_impl.h"
 
-#include <unordered_set>
-
 using namespace cfk_detail;
+
+namespace cfk_detail {
+
+int ensure_stage(als_engine* e) {
+    HIP_TRY(e->h_stage.reserve(32u << 20));
+    return ALS_OK;
+}
+
+}  // namespace cfk_detail
 
 namespace {
 
@@ -18,11 +25,6 @@ int check_factor_range(als_engine* e, int side, int64_t row0, int64_t n_rows, co
     if (!f.ptr) return fail(ALS_ERR_STATE, "factors of side %d not allocated/bound", side);
     if (row0 < 0 || n_rows < 0 || row0 + n_rows > f.n_rows) return fail(ALS_ERR_INVALID_ARGUMENT, "row range out of bounds");
     if (ld_value < e->k) return fail(ALS_ERR_INVALID_ARGUMENT, "%s (%lld) < num_features (%d)", ld, (long long)ld_value, e->k);
-    return ALS_OK;
-}
-
-int ensure_stage(als_engine* e) {
-    HIP_TRY(e->h_stage.reserve(32u << 20));
     return ALS_OK;
 }
 
@@ -528,321 +530,6 @@ int als_rank_targets(als_engine* e, const int64_t* user_rows, int64_t n_users, c
     const hipError_t st2 = hipStreamSynchronize(e->stream);
     if (st == hipSuccess) st = st2;
     if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_rank_targets: %s", hipGetErrorString(st));
-    return sync_checked(e);
-}
-
-// The query CSR and destination rows of als_fold_in / als_solve_implicit, checked in O(n_queries + entries); every
-// message names the query. *nnz_out = the entry count (below 2^31).
-static int check_queries(const char* fn, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
-                         const int64_t* dst_rows, const Factors& self, const Factors& opp, int64_t* nnz_out) {
-    const int64_t p0 = q_ptr[0];
-    if (p0 < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr[0] is negative", fn);
-    for (int64_t q = 0; q < n_queries; ++q)
-        if (q_ptr[q + 1] < q_ptr[q])
-            return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr decreases at query %lld", fn, (long long)q);
-    const int64_t nnz = q_ptr[n_queries] - p0;
-    if (nnz > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: the number of entries must be below 2^31", fn);
-    for (int64_t q = 0; q < n_queries; ++q)
-        for (int64_t x = q_ptr[q]; x < q_ptr[q + 1]; ++x)
-            if (q_idx[x] < 0 || q_idx[x] >= opp.n_rows)
-                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: index %d of query %lld is outside [0, %lld)", fn, (int)q_idx[x],
-                            (long long)q, (long long)opp.n_rows);
-    if (dst_rows) {
-        std::unordered_set<int64_t> seen;
-        seen.reserve((size_t)n_queries * 2);
-        for (int64_t q = 0; q < n_queries; ++q) {
-            if (dst_rows[q] < 0 || dst_rows[q] >= self.n_rows)
-                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows[%lld] = %lld of query %lld is outside [0, %lld)", fn,
-                            (long long)q, (long long)dst_rows[q], (long long)q, (long long)self.n_rows);
-            if (!seen.insert(dst_rows[q]).second)
-                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows repeats row %lld at query %lld", fn,
-                            (long long)dst_rows[q], (long long)q);
-        }
-    }
-    *nnz_out = nnz;
-    return ALS_OK;
-}
-
-int als_fold_in_plan(const als_engine* e, int64_t n_queries, int64_t info[4]) {
-    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
-    if (n_queries < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in_plan: n_queries < 0");
-    if (e->kp > cfk::FOLDIN_MAX_KP)
-        return fail(ALS_ERR_UNSUPPORTED, "als_fold_in: factor stride %d exceeds the supported %d", e->kp, cfk::FOLDIN_MAX_KP);
-    const cfk::FoldinPlan p = cfk::foldin_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
-    info[0] = p.threads;
-    info[1] = p.grid;
-    info[2] = p.batch;
-    info[3] = p.lds_bytes;
-    return ALS_OK;
-}
-
-int als_fold_in(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
-                const int16_t* q_ratings, float lambda, const int64_t* dst_rows, void* host_out, int64_t out_ld) {
-    if (int r = check_engine(e)) return r;
-    if (int r = check_side(side)) return r;
-    if (n_queries < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: n_queries < 0");
-    if (e->kp > cfk::FOLDIN_MAX_KP)
-        return fail(ALS_ERR_UNSUPPORTED, "als_fold_in: factor stride %d exceeds the supported %d", e->kp, cfk::FOLDIN_MAX_KP);
-    const Factors& self = e->fac[side];
-    const Factors& opp = e->fac[1 - side];
-    if (!opp.ptr) return fail(ALS_ERR_STATE, "als_fold_in: factors of side %d (the opposite side) not allocated/bound", 1 - side);
-    if (dst_rows && !self.ptr) return fail(ALS_ERR_STATE, "als_fold_in: dst_rows given but factors of side %d not allocated/bound", side);
-    if (n_queries == 0) return ALS_OK;
-    if (!q_ptr || !q_idx || !q_ratings) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: q_ptr, q_idx and q_ratings must be given");
-    if (!dst_rows && !host_out) return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: dst_rows and host_out are both NULL");
-    if (host_out && out_ld < e->k)
-        return fail(ALS_ERR_INVALID_ARGUMENT, "als_fold_in: out_ld (%lld) < num_features (%d)", (long long)out_ld, e->k);
-    if (!(lambda >= 0.f)) return fail(ALS_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
-    int64_t nnz = 0;
-    if (int r = check_queries("als_fold_in", n_queries, q_ptr, q_idx, dst_rows, self, opp, &nnz)) return r;
-    const int64_t p0 = q_ptr[0];
-    const cfk::FoldinPlan p = cfk::foldin_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
-    if (p.lds_bytes > cfk::FOLDIN_LDS_LIMIT) return fail(ALS_ERR_UNSUPPORTED, "als_fold_in: launch plan exceeds the LDS");
-    HIP_TRY(hipSetDevice(e->device));
-    if (int r = wait_gathers(e, true, true)) return r;
-    // workspace (256-byte aligned): rebased ranges, indices, ratings, destination rows, the kp-wide result rows
-    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const size_t row_bytes = (size_t)e->kp * e->elem();
-    const int64_t off_ptr = 0;
-    const int64_t off_idx = off_ptr + align((n_queries + 1) * 8);
-    const int64_t off_rat = off_idx + align(nnz * 4);
-    const int64_t off_dst = off_rat + align(nnz * 2);
-    const int64_t off_out = off_dst + (dst_rows ? align(n_queries * 8) : 0);
-    const size_t need = (size_t)off_out + (size_t)n_queries * row_bytes;
-    // als_recommend's workspace: all three calls are synchronous, so none is reading it when another starts
-    if (need > e->d_rec.size()) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        const hipError_t st = e->d_rec.reserve(need);
-        if (st != hipSuccess)
-            return fail(ALS_ERR_OUT_OF_MEMORY, "als_fold_in: device allocation (%zu bytes): %s", need, hipGetErrorString(st));
-    }
-    char* w = e->d_rec.get();
-    std::vector<int64_t> ptr0;   // the device ranges index the uploaded slice: rebased to 0
-    const int64_t* src = q_ptr;
-    if (p0 != 0) {
-        ptr0.resize(n_queries + 1);
-        for (int64_t q = 0; q <= n_queries; ++q) ptr0[q] = q_ptr[q] - p0;
-        src = ptr0.data();
-    }
-    cfk::FoldinArgs a{};
-    a.opp = opp.ptr;
-    a.self = self.ptr;
-    a.out = w + off_out;
-    a.q_ptr = (const int64_t*)(w + off_ptr);
-    a.q_idx = (const int32_t*)(w + off_idx);
-    a.q_rat = (const int16_t*)(w + off_rat);
-    a.dst_rows = dst_rows ? (const int64_t*)(w + off_dst) : nullptr;
-    a.n_queries = n_queries;
-    a.k = e->k;
-    a.lambda = lambda;
-    hipError_t st = hipMemcpyAsync(w + off_ptr, src, (n_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && nnz > 0)
-        st = hipMemcpyAsync(w + off_idx, q_idx + p0, nnz * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && nnz > 0)
-        st = hipMemcpyAsync(w + off_rat, q_ratings + p0, nnz * sizeof(int16_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && dst_rows)
-        st = hipMemcpyAsync(w + off_dst, dst_rows, n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
-    // read back the way als_read_factors does: whole kp-wide rows through the pinned staging buffer, the first k columns
-    // kept; a result that fits the buffer is queued behind the kernel, so the call waits for the stream once
-    const size_t es = e->elem();
-    int64_t rows_per = 0;
-    if (host_out) {
-        if (int r = ensure_stage(e)) return r;
-        rows_per = (int64_t)(e->h_stage.bytes() / row_bytes);
-    }
-    const bool one_pass = host_out && n_queries <= rows_per;
-    if (st == hipSuccess) st = cfk::launch_fold_in(e->precision, e->kp, a, p, e->stream);
-    if (st == hipSuccess && one_pass)
-        st = cfk::launch_download(w + off_out, e->h_stage.get(), (size_t)n_queries * row_bytes, e->stream);
-    // the host arrays (ptr0 too) are pageable: the stream has to pass the copies before this call returns
-    const hipError_t st2 = hipStreamSynchronize(e->stream);
-    if (st == hipSuccess) st = st2;
-    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_fold_in: %s", hipGetErrorString(st));
-    for (int64_t r = 0; host_out && r < n_queries; r += rows_per) {
-        const int64_t nr = std::min(rows_per, n_queries - r);
-        if (!one_pass) {
-            HIP_TRY(cfk::launch_download(w + off_out + (size_t)r * row_bytes, e->h_stage.get(), (size_t)nr * row_bytes,
-                                         e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-        }
-        const char* stage = (const char*)e->h_stage.get();
-        char* dst = (char*)host_out + (size_t)r * out_ld * es;
-        for (int64_t i = 0; i < nr; ++i)
-            std::memcpy(dst + (size_t)i * out_ld * es, stage + i * row_bytes, (size_t)e->k * es);
-    }
-    return sync_checked(e);
-}
-
-// The first k columns of n kp-wide device rows to host_out (row stride out_ld elements), through the pinned staging
-// buffer in as many passes as it takes. Waits for the stream.
-static int download_rows(als_engine* e, const char* fn, const char* d_rows, int64_t n, void* host_out, int64_t out_ld) {
-    if (int r = ensure_stage(e)) return r;
-    const size_t es = e->elem(), row_bytes = (size_t)e->kp * es;
-    const int64_t rows_per = (int64_t)(e->h_stage.bytes() / row_bytes);
-    for (int64_t r = 0; r < n; r += rows_per) {
-        const int64_t nr = std::min(rows_per, n - r);
-        hipError_t st = cfk::launch_download(d_rows + (size_t)r * row_bytes, e->h_stage.get(), (size_t)nr * row_bytes, e->stream);
-        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-        if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(st));
-        const char* stage = (const char*)e->h_stage.get();
-        char* dst = (char*)host_out + (size_t)r * out_ld * es;
-        for (int64_t i = 0; i < nr; ++i)
-            std::memcpy(dst + (size_t)i * out_ld * es, stage + i * row_bytes, (size_t)e->k * es);
-    }
-    return ALS_OK;
-}
-
-static int check_implicit_stride(const als_engine* e, const char* fn) {
-    if (e->kp > cfk::FOLDIN_MAX_KP)
-        return fail(ALS_ERR_UNSUPPORTED, "%s: factor stride %d exceeds the supported %d", fn, e->kp, cfk::FOLDIN_MAX_KP);
-    return ALS_OK;
-}
-
-int als_gram_table_plan(const als_engine* e, int64_t n_rows, int64_t info[4]) {
-    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
-    if (n_rows < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_gram_table_plan: n_rows < 0");
-    if (int r = check_implicit_stride(e, "als_gram_table")) return r;
-    const cfk::GramTablePlan p = cfk::gram_table_plan(e->kp, (int)e->elem(), n_rows, e->cu_count);
-    info[0] = p.threads;
-    info[1] = p.slabs;
-    info[2] = p.rows_per_slab;
-    info[3] = p.lds_bytes;
-    return ALS_OK;
-}
-
-int als_gram_table(als_engine* e, int side, void* host_out, int64_t out_ld) {
-    if (int r = check_engine(e)) return r;
-    if (int r = check_side(side)) return r;
-    if (int r = check_implicit_stride(e, "als_gram_table")) return r;
-    const Factors& tab = e->fac[side];
-    if (!tab.ptr) return fail(ALS_ERR_STATE, "als_gram_table: factors of side %d not allocated/bound", side);
-    if (!host_out) return fail(ALS_ERR_INVALID_ARGUMENT, "als_gram_table: host_out is NULL");
-    if (out_ld < e->k)
-        return fail(ALS_ERR_INVALID_ARGUMENT, "als_gram_table: out_ld (%lld) < num_features (%d)", (long long)out_ld, e->k);
-    const cfk::GramTablePlan p = cfk::gram_table_plan(e->kp, (int)e->elem(), tab.n_rows, e->cu_count);
-    HIP_TRY(hipSetDevice(e->device));
-    if (int r = wait_gathers(e, true, true)) return r;
-    // als_recommend's workspace: the kp x kp result, then the slabs' tiles
-    const size_t gram_bytes = ((size_t)e->kp * e->kp * e->elem() + 255) / 256 * 256;
-    const size_t need = gram_bytes + (size_t)p.partial_bytes;
-    if (need > e->d_rec.size()) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        const hipError_t st = e->d_rec.reserve(need);
-        if (st != hipSuccess)
-            return fail(ALS_ERR_OUT_OF_MEMORY, "als_gram_table: device allocation (%zu bytes): %s", need, hipGetErrorString(st));
-    }
-    char* w = e->d_rec.get();
-    const hipError_t st = cfk::launch_gram_table(e->precision, e->kp, tab.ptr, tab.n_rows, p, w + gram_bytes, w, e->stream);
-    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_gram_table: %s", hipGetErrorString(st));
-    if (int r = download_rows(e, "als_gram_table", w, e->k, host_out, out_ld)) return r;
-    return sync_checked(e);
-}
-
-int als_solve_implicit_plan(const als_engine* e, int64_t n_queries, int64_t info[4]) {
-    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
-    if (n_queries < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "als_solve_implicit_plan: n_queries < 0");
-    if (int r = check_implicit_stride(e, "als_solve_implicit")) return r;
-    const cfk::FoldinPlan p = cfk::implicit_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
-    info[0] = p.threads;
-    info[1] = p.grid;
-    info[2] = p.batch;
-    info[3] = p.lds_bytes;
-    return ALS_OK;
-}
-
-int als_solve_implicit(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
-                       const int16_t* q_ratings, float lambda, float alpha, const int64_t* dst_rows, void* host_out,
-                       int64_t out_ld) {
-    static const char* fn = "als_solve_implicit";
-    if (int r = check_engine(e)) return r;
-    if (int r = check_side(side)) return r;
-    if (n_queries < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: n_queries < 0", fn);
-    if (int r = check_implicit_stride(e, fn)) return r;
-    const Factors& self = e->fac[side];
-    const Factors& opp = e->fac[1 - side];
-    if (!opp.ptr) return fail(ALS_ERR_STATE, "%s: factors of side %d (the opposite side) not allocated/bound", fn, 1 - side);
-    if (dst_rows && !self.ptr) return fail(ALS_ERR_STATE, "%s: dst_rows given but factors of side %d not allocated/bound", fn, side);
-    if (!(lambda > 0.f) || !std::isfinite(lambda))
-        return fail(ALS_ERR_INVALID_ARGUMENT, "%s: lambda must be positive and finite", fn);
-    if (!(alpha > 0.f) || !std::isfinite(alpha))
-        return fail(ALS_ERR_INVALID_ARGUMENT, "%s: alpha must be positive and finite", fn);
-    if (n_queries == 0) return ALS_OK;
-    if (!q_ptr || !q_idx || !q_ratings) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr, q_idx and q_ratings must be given", fn);
-    if (!dst_rows && !host_out) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows and host_out are both NULL", fn);
-    if (host_out && out_ld < e->k)
-        return fail(ALS_ERR_INVALID_ARGUMENT, "%s: out_ld (%lld) < num_features (%d)", fn, (long long)out_ld, e->k);
-    int64_t nnz = 0;
-    if (int r = check_queries(fn, n_queries, q_ptr, q_idx, dst_rows, self, opp, &nnz)) return r;
-    const int64_t p0 = q_ptr[0];
-    for (int64_t q = 0; q < n_queries; ++q)
-        for (int64_t x = q_ptr[q]; x < q_ptr[q + 1]; ++x)
-            if (q_ratings[x] < 0)
-                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: rating %d of query %lld is negative", fn, (int)q_ratings[x], (long long)q);
-    const cfk::FoldinPlan p = cfk::implicit_plan(e->kp, (int)e->elem(), n_queries, e->cu_count);
-    if (p.lds_bytes > cfk::FOLDIN_LDS_LIMIT) return fail(ALS_ERR_UNSUPPORTED, "%s: launch plan exceeds the LDS", fn);
-    const cfk::GramTablePlan gp = cfk::gram_table_plan(e->kp, (int)e->elem(), opp.n_rows, e->cu_count);
-    // rebased ranges, and the order the workgroups take the queries in: longest first (stable), so that the one long
-    // query of a training half starts first instead of last. Results do not depend on it.
-    std::vector<int64_t> ptr0(n_queries + 1), order(n_queries);
-    for (int64_t q = 0; q <= n_queries; ++q) ptr0[q] = q_ptr[q] - p0;
-    for (int64_t q = 0; q < n_queries; ++q) order[q] = q;
-    std::stable_sort(order.begin(), order.end(),
-                     [&](int64_t x, int64_t y) { return ptr0[x + 1] - ptr0[x] > ptr0[y + 1] - ptr0[y]; });
-    HIP_TRY(hipSetDevice(e->device));
-    if (int r = wait_gathers(e, true, true)) return r;
-    // workspace (256-byte aligned), als_recommend's: ranges, order, indices, ratings, destination rows, the opposite
-    // table's Gram and its slabs' tiles, the kp-wide result rows
-    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const size_t row_bytes = (size_t)e->kp * e->elem();
-    const int64_t off_ptr = 0;
-    const int64_t off_ord = off_ptr + align((n_queries + 1) * 8);
-    const int64_t off_idx = off_ord + align(n_queries * 8);
-    const int64_t off_rat = off_idx + align(nnz * 4);
-    const int64_t off_dst = off_rat + align(nnz * 2);
-    const int64_t off_gram = off_dst + (dst_rows ? align(n_queries * 8) : 0);
-    const int64_t off_part = off_gram + align((int64_t)e->kp * (int64_t)row_bytes);
-    const int64_t off_out = off_part + align(gp.partial_bytes);
-    const size_t need = (size_t)off_out + (size_t)n_queries * row_bytes;
-    if (need > e->d_rec.size()) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        const hipError_t st = e->d_rec.reserve(need);
-        if (st != hipSuccess)
-            return fail(ALS_ERR_OUT_OF_MEMORY, "%s: device allocation (%zu bytes): %s", fn, need, hipGetErrorString(st));
-    }
-    char* w = e->d_rec.get();
-    cfk::ImplicitArgs a{};
-    a.f.opp = opp.ptr;
-    a.f.self = self.ptr;
-    a.f.out = w + off_out;
-    a.f.q_ptr = (const int64_t*)(w + off_ptr);
-    a.f.q_idx = (const int32_t*)(w + off_idx);
-    a.f.q_rat = (const int16_t*)(w + off_rat);
-    a.f.dst_rows = dst_rows ? (const int64_t*)(w + off_dst) : nullptr;
-    a.f.n_queries = n_queries;
-    a.f.k = e->k;
-    a.f.lambda = lambda;
-    a.gram = w + off_gram;
-    a.order = (const int64_t*)(w + off_ord);
-    a.alpha = alpha;
-    hipError_t st = hipMemcpyAsync(w + off_ptr, ptr0.data(), (n_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess)
-        st = hipMemcpyAsync(w + off_ord, order.data(), n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && nnz > 0)
-        st = hipMemcpyAsync(w + off_idx, q_idx + p0, nnz * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && nnz > 0)
-        st = hipMemcpyAsync(w + off_rat, q_ratings + p0, nnz * sizeof(int16_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && dst_rows)
-        st = hipMemcpyAsync(w + off_dst, dst_rows, n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
-    // G of the opposite table, recomputed on every call: no per-engine state that could go stale
-    if (st == hipSuccess)
-        st = cfk::launch_gram_table(e->precision, e->kp, opp.ptr, opp.n_rows, gp, w + off_part, w + off_gram, e->stream);
-    if (st == hipSuccess) st = cfk::launch_implicit(e->precision, e->kp, a, p, e->stream);
-    // the host arrays are pageable: the stream has to pass the copies before this call returns
-    const hipError_t st2 = hipStreamSynchronize(e->stream);
-    if (st == hipSuccess) st = st2;
-    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(st));
-    if (host_out)
-        if (int r = download_rows(e, fn, w + off_out, n_queries, host_out, out_ld)) return r;
     return sync_checked(e);
 }
 

@@ -1,7 +1,7 @@
 // Private to als_foldin.hip and als_implicit.hip: what a 256-thread workgroup needs to form lower-triangle 16 x 16 MFMA
 // Gram tiles of staged rows at full input precision -- the accumulator types, the tile maps, the per-wave batch product
-// and tile store, and the two-half batch staging (FoldBatch / fold_load / fold_store). Moved here from als_foldin.hip
-// unchanged; the layout is described there and in DESIGN.md section 3.9. Include inside namespace cfk { namespace {.
+// and tile store, and the two-half batch staging (FoldBatch / fold_load / fold_store). The layout is described in
+// als_fold_solve.h and in DESIGN.md section 3.9. Include inside namespace cfk { namespace {.
 #pragma once
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -49,10 +49,13 @@ __device__ __forceinline__ void fold_gram_batch(typename FoldAcc<T>::type (&acc)
     }
 }
 
-// The tiles of wave W from their accumulators into the LDS triangle. C/D map of the f32 form: column = lane & 15,
+// The tiles of wave W from their accumulators into a tiled triangle [NT][16][PITCH]: the LDS triangle of the solve
+// (FOLDIN_TILE_PITCH) or a slab's dense partial tiles of the table Gram (16). C/D map of the f32 form: column = lane & 15,
 // row = 4 (lane >> 4) + r; of the f64 form: row = (lane >> 4) + 4 r.
-template <class T, int KP, int W, int MT>
-__device__ __forceinline__ void fold_store_tiles(const typename FoldAcc<T>::type (&acc)[MT], T* __restrict__ G, int lane) {
+template <int PITCH> using FoldTilePitch = std::integral_constant<int, PITCH>;
+template <class T, int KP, int W, int MT, int PITCH>
+__device__ __forceinline__ void fold_store_tiles(const typename FoldAcc<T>::type (&acc)[MT], T* __restrict__ G, int lane,
+                                                 FoldTilePitch<PITCH>) {
     constexpr int NT = foldin_tiles(KP);
     constexpr bool F64 = std::is_same<T, double>::value;
     const int g = lane >> 4, c = lane & 15;
@@ -62,7 +65,7 @@ __device__ __forceinline__ void fold_store_tiles(const typename FoldAcc<T>::type
             static_for<0, 4>([&](auto r) {
                 constexpr int rr = decltype(r)::value;
                 const int row = F64 ? g + 4 * rr : 4 * g + rr;
-                G[tt * FOLDIN_TILE_ELEMS + row * FOLDIN_TILE_PITCH + c] = acc[tt / 4][rr];
+                G[tt * (16 * PITCH) + row * PITCH + c] = acc[tt / 4][rr];
             });
         }
     });

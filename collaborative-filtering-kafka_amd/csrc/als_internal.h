@@ -1,5 +1,5 @@
 // Internal declarations shared by the engine (als_engine*.cpp, their state: als_engine_impl.h) and the kernels
-// (als_kernels.hip, als_recommend.hip, als_rank.hip, als_build.hip).
+// (als_kernels.hip, als_recommend.hip, als_rank.hip, als_foldin.hip, als_implicit.hip, als_build.hip).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -139,7 +139,7 @@ hipError_t launch_rank(int precision, const void* U, const void* M, int kp, int 
 // Fold-in (als_foldin.hip), all arrays on the device: query q solves x = (Y^T Y + lambda n I)^-1 Y^T r over the opposite
 // rows q_idx[q_ptr[q] .. q_ptr[q + 1]) (q_ptr[0] = 0) with the ratings q_rat, n their count; n = 0 gives zeros. Row q of
 // `out` ([n_queries][kp], columns >= k zero) always receives it, and so does row dst_rows[q] of `self` when dst_rows is
-// not NULL. kp: 16, 32, 64 or 128; the geometry is foldin_plan's (als_plan.h).
+// not NULL. kp: 16, 32, 64 or 128, and in fp64 also 80, 96 or 112; the geometry is foldin_plan's (als_plan.h).
 struct FoldinArgs {
     const void* opp;          // opposite factor matrix [n_opp][kp], the plain table
     void* self;               // this side's factor matrix (read only with dst_rows)
