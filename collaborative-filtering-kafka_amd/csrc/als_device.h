@@ -73,6 +73,14 @@ __device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void pin(double& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void pin(unsigned& v) { asm volatile("" : "+v"(v)); }
 
+// A load of data its launch touches exactly once, under the buffer's policy (CachePolicy, als_internal.h): STREAM sets
+// the access's `nt` bit and nothing else -- width, alignment and address form are those of the plain load.
+template <bool STREAM, class T>
+__device__ __forceinline__ T load_stream(const T* p) {
+    if constexpr (STREAM) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
 __device__ __forceinline__ Task load_task(const Task* p) {
     Task t = *p;
     t.begin = ((int64_t)uni((int)(t.begin >> 32)) << 32) | (int64_t)(uint32_t)uni((int)(uint32_t)t.begin);

@@ -44,6 +44,13 @@ struct SolveArgs {
     int32_t grid_cap;       // workgroups of a grid-stride launch (the range guard's fallback): CUs x 4
     int32_t extra_lds;      // diagnostics (debug build's ALS_DEBUG_EXTRA_LDS, else 0): unused dynamic LDS per workgroup
 };
+// Cache policy of the buffers a solve launch touches exactly once (load_stream, als_device.h): true = the access
+// carries the streaming (non-temporal) policy. One constant per buffer that measured faster with it; every other
+// buffer -- the gathered opposite rows, which a launch reuses, and every one-touch stream that measured no gain or a
+// loss -- keeps the default policy and has no entry here.
+struct CachePolicy {
+    static constexpr bool slot_loads = true;   // the REDUCE launch's loads of the partial slots (als_slots.h)
+};
 // Factor row of local row `row` under the block's slot layout (wave-uniform: scalar arithmetic, once per task).
 __host__ __device__ inline int64_t factor_row(int64_t row_offset, int32_t rows_per_chunk, int64_t chunk_stride,
                                               int32_t row) {

@@ -110,10 +110,12 @@ __device__ __forceinline__ void sum_partial_slots(const SolveArgs& a, const Task
         const float* src = part + (int64_t)(tk.slot + s) * (SLOT_WORDS * 64) + lane;
         SlotCodec cd{slot_key(a.gen, tk.slot + s, lane)};
         // the whole slot's loads are issued before the first use: left to the scheduler under the KP = 128
-        // register pressure they went out one at a time (load, wait, add: 0.44 ms for 974 rows)
+        // register pressure they went out one at a time (load, wait, add: 0.44 ms for 974 rows). Streaming loads: a
+        // slot is read once, by this wave alone (the k = 64 movie REDUCE 0.049 -> 0.045 ms; the stores of
+        // store_partial measured no gain with the same policy and keep the default)
         float w[SLOT_WORDS];
 #pragma unroll
-        for (int q = 0; q < SLOT_WORDS; ++q) w[q] = src[q * 64];
+        for (int q = 0; q < SLOT_WORDS; ++q) w[q] = load_stream<CachePolicy::slot_loads>(src + q * 64);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int p = 0; p < Acc::NT; ++p)

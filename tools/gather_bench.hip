@@ -8,8 +8,16 @@
 //      vector-memory instructions per block), uniform rows
 //   3  LDS-DMA with the rows below HOT left out of the DMA (exec-masked lanes: rows an LDS-resident hot-row cache
 //      would serve), the reads as mode 0
+//   5  (--stream) LDS-DMA as mode 0 plus the rating words of the block: with the 128 B of row indices the same 256 B of
+//      one-touch index / rating loads a pre-split Gram block performs (als_gram_presplit.h: 16 B of indices per lane,
+//      16 B of rating pairs per lane, the rh half for lanes 0-7 of a row group and the rm half for lanes 8-15), default
+//      cache policy
+//   6  (--stream) mode 5 with both one-touch loads non-temporal (__builtin_nontemporal_load); the gathers keep the
+//      default policy in both
 // over uniform rows and over the Netflix-shape movie popularity (rank + 321)^-1.85 (ids = popularity ranks, so
-// "row < HOT" is the HOT most popular rows).
+// "row < HOT" is the HOT most popular rows). --stream runs modes 5 and 6 alone, on both tables, over uniform rows and
+// over that law (stretched to the table's row count on the 123 MB table): the bound on what a streaming policy on the
+// index and rating loads can give either half.
 // one block in flight per wave (DEPTH 1; the index loads of a block follow the previous block's wait, so a deeper
 // pipeline would need its own counted waits). Prints GB/s for each mode and table size.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/gather_bench.hip -o build/gather_bench
@@ -20,6 +28,7 @@
 #include <random>
 #include <cmath>
 #include <algorithm>
+#include <string>
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 
@@ -33,13 +42,17 @@ constexpr int IMG = BLK_ROWS * ROW;   // 8 KB per block
 // idx layout: [block][g = lane >> 4][m = 0..7] = row of entry 4 m + g of the block
 template <int MODE, int DEPTH>
 __global__ __launch_bounds__(64 * WAVES) void gather(const char* __restrict__ table, const int* __restrict__ idx,
-                                                     int nblk_per_wave, unsigned* __restrict__ sink, int hot) {
+                                                     int nblk_per_wave, unsigned* __restrict__ sink, int hot,
+                                                     const unsigned* __restrict__ rat = nullptr) {
     __shared__ __attribute__((aligned(1024))) char img[WAVES][DEPTH][IMG];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gw = blockIdx.x * WAVES + wave;
     const int g = lane >> 4, c = lane & 15;
     const int* ip = idx + ((int64_t)gw * nblk_per_wave) * 32 + g * 8;
     unsigned acc = 0;
+    constexpr bool DMA = MODE == 0 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 6;
+    // modes 5, 6: 128 B of rating words per block, [block][half = c >> 3][g]: 16 B per lane
+    const u32x4* rp = (const u32x4*)(rat + ((int64_t)gw * nblk_per_wave) * 32) + 4 * (c >> 3) + g;
     auto load_rows = [&](int b, int (&rows)[8]) {
         if constexpr (MODE == 4) {
             for (int m = 0; m < 8; ++m) {
@@ -51,11 +64,23 @@ __global__ __launch_bounds__(64 * WAVES) void gather(const char* __restrict__ ta
             }
             return;
         }
-        const i32x4 r0 = *(const i32x4*)(ip + (int64_t)b * 32);
-        const i32x4 r1 = *(const i32x4*)(ip + (int64_t)b * 32 + 4);
+        i32x4 r0, r1;
+        if constexpr (MODE == 6) {
+            r0 = __builtin_nontemporal_load((const i32x4*)(ip + (int64_t)b * 32));
+            r1 = __builtin_nontemporal_load((const i32x4*)(ip + (int64_t)b * 32 + 4));
+            const u32x4 r = __builtin_nontemporal_load(rp + (int64_t)b * 8);
+            acc ^= r[0] ^ r[1] ^ r[2] ^ r[3];
+        } else {
+            r0 = *(const i32x4*)(ip + (int64_t)b * 32);
+            r1 = *(const i32x4*)(ip + (int64_t)b * 32 + 4);
+            if constexpr (MODE == 5) {
+                const u32x4 r = rp[(int64_t)b * 8];
+                acc ^= r[0] ^ r[1] ^ r[2] ^ r[3];
+            }
+        }
         for (int m = 0; m < 4; ++m) { rows[m] = r0[m]; rows[4 + m] = r1[m]; }
     };
-    if constexpr (MODE == 0 || MODE == 3 || MODE == 4) {
+    if constexpr (DMA) {
         auto issue = [&](int b, char* im) {
             int rows[8];
             load_rows(b, rows);
@@ -111,16 +136,16 @@ __global__ __launch_bounds__(64 * WAVES) void gather(const char* __restrict__ ta
 
 template <int MODE, int DEPTH>
 int run(const char* table, const int* idx, int grid, int nblk, unsigned* sink, const char* label, int64_t tbytes,
-        int hot = 0) {
+        int hot = 0, const unsigned* rat = nullptr) {
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
-    gather<MODE, DEPTH><<<grid, 64 * WAVES>>>(table, idx, nblk, sink, hot);
+    gather<MODE, DEPTH><<<grid, 64 * WAVES>>>(table, idx, nblk, sink, hot, rat);
     CHECK(hipDeviceSynchronize());
     float best = 1e30f;
     for (int it = 0; it < 5; ++it) {
         CHECK(hipEventRecord(e0));
-        gather<MODE, DEPTH><<<grid, 64 * WAVES>>>(table, idx, nblk, sink, hot);
+        gather<MODE, DEPTH><<<grid, 64 * WAVES>>>(table, idx, nblk, sink, hot, rat);
         CHECK(hipEventRecord(e1));
         CHECK(hipEventSynchronize(e1));
         float ms;
@@ -133,7 +158,18 @@ int run(const char* table, const int* idx, int grid, int nblk, unsigned* sink, c
     return 0;
 }
 
-int main() {
+// Ranks drawn from P(rank) ~ (rank + a)^-1.85 over `rows` rows (inverse CDF of the continuous law).
+static void fill_zipf(std::vector<int>& h, std::mt19937& rng, int64_t rows, double a) {
+    std::uniform_real_distribution<double> U(0.0, 1.0);
+    const double e = 0.85, top = std::pow(a, -e), bot = std::pow(a + rows, -e);
+    for (auto& x : h) {
+        const double r = std::pow(top - U(rng) * (top - bot), -1.0 / e) - a;
+        x = std::min<int>((int)rows - 1, std::max(0, (int)r));
+    }
+}
+
+int main(int argc, char** argv) {
+    const bool stream = argc > 1 && std::string(argv[1]) == "--stream";
     const int cus = 256, wg_per_cu = 4, grid = cus * wg_per_cu;   // 16 waves per CU
     const int nblk = 200;
     const int64_t nrows_idx = (int64_t)grid * WAVES * nblk * 32;
@@ -141,6 +177,38 @@ int main() {
     unsigned* d_sink;
     CHECK(hipMalloc(&d_idx, nrows_idx * 4));
     CHECK(hipMalloc(&d_sink, (size_t)grid * WAVES * 4));
+    if (stream) {
+        unsigned* d_rat;   // 4 B per gathered row, as the fp16 rating pairs (rh and rm) are
+        CHECK(hipMalloc(&d_rat, nrows_idx * 4));
+        CHECK(hipMemset(d_rat, 1, nrows_idx * 4));
+        for (int64_t rows : {17771LL, 480190LL}) {
+            const int64_t tbytes = rows * ROW;
+            char* d_table;
+            CHECK(hipMalloc(&d_table, tbytes));
+            CHECK(hipMemset(d_table, 1, tbytes));
+            std::vector<int> h(nrows_idx);
+            std::mt19937 rng(7);
+            for (int skew = 0; skew < 2; ++skew) {
+                if (skew) {
+                    fill_zipf(h, rng, rows, 321.0 * (double)rows / 17771.0);
+                } else {
+                    std::uniform_int_distribution<int> dist(0, (int)rows - 1);
+                    for (auto& x : h) x = dist(rng);
+                }
+                CHECK(hipMemcpy(d_idx, h.data(), nrows_idx * 4, hipMemcpyHostToDevice));
+                // default / streaming / default / streaming: the second pair shows the run-to-run spread
+                for (int rep = 0; rep < 2; ++rep) {
+                    if (run<5, 1>(d_table, d_idx, grid, nblk, d_sink, skew ? "zipf idx+rat default" : "idx+rat default",
+                                  tbytes, 0, d_rat)) return 1;
+                    if (run<6, 1>(d_table, d_idx, grid, nblk, d_sink, skew ? "zipf idx+rat streaming" : "idx+rat streaming",
+                                  tbytes, 0, d_rat)) return 1;
+                }
+            }
+            CHECK(hipFree(d_table));
+        }
+        printf("gather_bench --stream done\n");
+        return 0;
+    }
     for (int64_t rows : {17771LL, 480190LL}) {
         const int64_t tbytes = rows * ROW;
         char* d_table;
@@ -157,12 +225,7 @@ int main() {
         if (run<4, 1>(d_table, d_idx, grid, nblk, d_sink, "LDS-DMA, no index loads", tbytes, (int)rows)) return 1;
         if (rows == 17771) {
             // Netflix-shape popularity: id = rank, P(rank) ~ (rank + 321)^-1.85 (inverse CDF of the continuous law)
-            std::uniform_real_distribution<double> U(0.0, 1.0);
-            const double a = 321.0, e = 0.85, top = std::pow(a, -e), bot = std::pow(a + rows, -e);
-            for (auto& x : h) {
-                const double r = std::pow(top - U(rng) * (top - bot), -1.0 / e) - a;
-                x = std::min<int>((int)rows - 1, std::max(0, (int)r));
-            }
+            fill_zipf(h, rng, rows, 321.0);
             CHECK(hipMemcpy(d_idx, h.data(), nrows_idx * 4, hipMemcpyHostToDevice));
             for (int hot : {0, 64, 112, 240, 480}) {
                 int64_t n = 0;

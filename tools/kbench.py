@@ -5,6 +5,9 @@
   CFK_ALS_LIB=collaborative-filtering-kafka_amd/build_debug/libcfk_als.so python tools/kbench.py \
       --variants "ALS_DEBUG_SKIP_SOLVE=0" "ALS_DEBUG_SKIP_SOLVE=1"   # Gram / solve split: debug build only
 
+  python tools/kbench.py --libs build_parent build   # A/B of library builds (collaborative-filtering-kafka_amd/<dir>/
+      libcfk_als.so), every build loaded into this one process, rounds interleaved over builds x variants
+
 Each variant is a set of env settings read at engine creation / block upload. Prints per-variant median and
 min device time (HIP events) of the main + reduce launches of each half on the Netflix-shape workload. Every
 timed half starts from the same snapshot of real factor tables (two iterations from the seeded U0).
@@ -31,11 +34,41 @@ def main():
     ap.add_argument("--movies", type=int, default=17_770)
     ap.add_argument("--nnz", type=int, default=100_000_000)
     ap.add_argument("--shard-of", type=int, default=1, help="G > 1: shard 0 of G (one rank's blocks, bench --shard-of)")
+    ap.add_argument("--libs", nargs="+", default=None, metavar="BUILD_DIR",
+                    help="library builds to compare in this process; a variant is then named '<build dir>:<env>'")
     args = ap.parse_args()
+    import importlib.util
     import numpy as np
     import torch
     import __graft_entry__
-    cfk = __graft_entry__.load_package()
+
+    def load_build(i, build_dir):
+        """The package once more under its own module name, bound to the library of `build_dir` (its _lib reads
+        CFK_ALS_LIB when it is imported)."""
+        saved = os.environ.get("CFK_ALS_LIB")
+        os.environ["CFK_ALS_LIB"] = os.path.join(__graft_entry__.PKG_DIR, build_dir, "libcfk_als.so")
+        try:
+            name = f"{__graft_entry__.PKG_NAME}_build{i}"
+            spec = importlib.util.spec_from_file_location(name, os.path.join(__graft_entry__.PKG_DIR, "__init__.py"),
+                                                          submodule_search_locations=[__graft_entry__.PKG_DIR])
+            mod = importlib.util.module_from_spec(spec)
+            sys.modules[name] = mod
+            spec.loader.exec_module(mod)
+            sys.modules[name + "._lib"].lib()
+        finally:
+            if saved is None:
+                del os.environ["CFK_ALS_LIB"]
+            else:
+                os.environ["CFK_ALS_LIB"] = saved
+        return mod
+
+    if args.libs:
+        pkgs = {d: load_build(i, d) for i, d in enumerate(args.libs)}
+        cfk = pkgs[args.libs[0]]
+        args.variants = [f"{d}:{v}" for v in args.variants for d in args.libs]
+    else:
+        cfk = __graft_entry__.load_package()
+        pkgs = {}
     G = args.shard_of
     if G > 1:
         ds = cfk.Dataset.synthetic_shard("netflix", args.users, args.movies, args.nnz, 0xA15, G, 0, nthreads=16)
@@ -49,12 +82,16 @@ def main():
                 torch.zeros((blocks[1]["n_slots"] + 1, kp), dtype=torch.float32, device="cuda"))
 
     def make_engine(env, M, U):
+        pkg = cfk
+        if args.libs and ":" in env:
+            d, env = env.split(":", 1)
+            pkg = pkgs[d]
         saved = dict(os.environ)
         for kv in env.split(","):
             if kv:
                 k, val = kv.split("=")
                 os.environ[k] = val
-        eng = cfk.ALSEngine(args.k, "f32")
+        eng = pkg.ALSEngine(args.k, "f32")
         eng.use_torch_stream()
         eng.bind_factors(0, M)
         eng.bind_factors(1, U)
@@ -122,7 +159,7 @@ def main():
         print("vs", args.variants[0], ":", v, json.dumps(d), flush=True)
     out = {}
     for v in args.variants:
-        out[v] = {k: {"median_ms": statistics.median(x), "min_ms": min(x)} for k, x in res[v].items()}
+        out[v] = {k: {"median_ms": statistics.median(x), "min_ms": min(x), "max_ms": max(x)} for k, x in res[v].items()}
         out[v]["total_median_ms"] = sum(out[v][k]["median_ms"] for k in ("movie", "user", "movie_reduce", "user_reduce"))
         print(v, json.dumps(out[v]), flush=True)
     print(json.dumps({"kbench": out, "nnz": args.nnz, "k": args.k, "diffs": diffs}))
