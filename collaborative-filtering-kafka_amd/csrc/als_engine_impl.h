@@ -1,8 +1,9 @@
 // als_engine_impl.h -- the engine's state and the helpers its translation units share: als_engine.cpp (lifetime,
 // environment, streams, synchronisation, timing, introspection), als_engine_block.cpp (block upload, chunks, row
-// layout), als_engine_solve.cpp (factors, the half-iteration launch, squared error, predict, recommend, held-out
-// ranks), als_engine_query.cpp (fold-in, the implicit solve, the table Gram) and als_engine_comm.cpp (the RCCL
-// exchange). Private to csrc/.
+// layout), als_engine_solve.cpp (factor buffers and their I/O, the half-iteration launch, squared error),
+// als_engine_score.cpp (predict, recommend, held-out ranks), als_engine_query.cpp (fold-in, the implicit solve, the
+// table Gram) and als_engine_comm.cpp (the RCCL exchange). The synchronous calls of the score and query units share
+// one host path, als_engine_call.h, and the checks of their CSR arguments, als_args.h (host-only). Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -155,9 +156,10 @@ struct als_engine {
                                     //   words of the pre-split table, used in turn), then per side the exponent its
                                     //   opposite table was last split at
     int prep_set = 0;               // the set of the last preparation: SolveArgs::amax of the half it served
-    cfk::DeviceBuf<char> d_rec;     // als_recommend's own grow-only workspace (rows, exclusion CSR, partial and final
-                                    //   lists): never d_partials / d_split / d_prep, which a half in progress owns.
-                                    //   als_rank_targets uses it too: both calls are synchronous
+    cfk::DeviceBuf<char> d_rec;     // the grow-only workspace of the synchronous calls (als_recommend, als_rank_targets,
+                                    //   als_fold_in, als_solve_implicit, als_gram_table; als_engine_call.h): none of
+                                    //   them is reading it when another starts. Never d_partials / d_split / d_prep,
+                                    //   which a half in progress owns
     cfk::PinnedBuf h_stage;         // pinned staging of als_write_factors / als_read_factors (copy kernels)
     cfk::DeviceBuf<uint32_t> d_integrity;   // cfk::INTEGRITY_WORDS: partial slots that failed their check
     int cu_count = 0;               // compute units of the device: the range guard's fallback grid
@@ -190,5 +192,10 @@ int sync_checked(als_engine* e);
 // Make sure the pinned staging buffer (h_stage) of the factor I/O and the query read-back exists
 // (als_engine_solve.cpp).
 int ensure_stage(als_engine* e);
+// The first k columns of the nr kp-wide rows in the pinned staging buffer to host_out (row stride out_ld elements).
+void unpack_stage(const als_engine* e, int64_t nr, void* host_out, int64_t out_ld);
+// The first k columns of n kp-wide device rows to host_out, through the pinned staging buffer in as many passes as it
+// takes (als_engine_solve.cpp). Waits for the stream once per pass; `fn` names the call in a failure's message.
+int download_rows(als_engine* e, const char* fn, const char* d_rows, int64_t n, void* host_out, int64_t out_ld);
 
 }  // namespace cfk_detail

@@ -1,11 +1,10 @@
 // als_engine_query.cpp -- the calls that solve ad-hoc queries against the resident factors: als_fold_in (the explicit
 // normal equation) and als_solve_implicit (implicit feedback) over one host path, solve_queries, with als_gram_table
-// and the three *_plan calls. All of them are synchronous, keep no per-engine state and work in d_rec, the grow-only
-// workspace of als_recommend / als_rank_targets: none of those calls is reading it when another starts.
-#include "als_engine_impl.h"
+// and the three *_plan calls. All of them are synchronous, on the host path of als_engine_call.h, and keep no
+// per-engine state.
+#include "als_engine_call.h"
 
 #include <cmath>
-#include <unordered_set>
 
 using namespace cfk_detail;
 
@@ -22,70 +21,6 @@ int check_plan_call(const als_engine* e, const int64_t* info, const char* fn, co
     if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
     if (n < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s_plan: %s < 0", fn, count);
     return check_stride(e, fn);
-}
-
-int plan_info(int64_t info[4], int64_t threads, int64_t groups, int64_t per_group, int64_t lds_bytes) {
-    info[0] = threads;
-    info[1] = groups;
-    info[2] = per_group;
-    info[3] = lds_bytes;
-    return ALS_OK;
-}
-
-// The query CSR and destination rows of als_fold_in / als_solve_implicit, checked in O(n_queries + entries); every
-// message names the query. *nnz_out = the entry count (below 2^31).
-int check_queries(const char* fn, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx, const int64_t* dst_rows,
-                  const Factors& self, const Factors& opp, int64_t* nnz_out) {
-    const int64_t p0 = q_ptr[0];
-    if (p0 < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr[0] is negative", fn);
-    for (int64_t q = 0; q < n_queries; ++q)
-        if (q_ptr[q + 1] < q_ptr[q])
-            return fail(ALS_ERR_INVALID_ARGUMENT, "%s: q_ptr decreases at query %lld", fn, (long long)q);
-    const int64_t nnz = q_ptr[n_queries] - p0;
-    if (nnz > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "%s: the number of entries must be below 2^31", fn);
-    for (int64_t q = 0; q < n_queries; ++q)
-        for (int64_t x = q_ptr[q]; x < q_ptr[q + 1]; ++x)
-            if (q_idx[x] < 0 || q_idx[x] >= opp.n_rows)
-                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: index %d of query %lld is outside [0, %lld)", fn, (int)q_idx[x],
-                            (long long)q, (long long)opp.n_rows);
-    if (dst_rows) {
-        std::unordered_set<int64_t> seen;
-        seen.reserve((size_t)n_queries * 2);
-        for (int64_t q = 0; q < n_queries; ++q) {
-            if (dst_rows[q] < 0 || dst_rows[q] >= self.n_rows)
-                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows[%lld] = %lld of query %lld is outside [0, %lld)", fn,
-                            (long long)q, (long long)dst_rows[q], (long long)q, (long long)self.n_rows);
-            if (!seen.insert(dst_rows[q]).second)
-                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: dst_rows repeats row %lld at query %lld", fn,
-                            (long long)dst_rows[q], (long long)q);
-        }
-    }
-    *nnz_out = nnz;
-    return ALS_OK;
-}
-
-// The first k columns of the nr kp-wide rows in the pinned staging buffer to host_out (row stride out_ld elements).
-void unpack_stage(const als_engine* e, int64_t nr, void* host_out, int64_t out_ld) {
-    const size_t es = e->elem(), row_bytes = (size_t)e->kp * es;
-    const char* stage = (const char*)e->h_stage.get();
-    for (int64_t i = 0; i < nr; ++i)
-        std::memcpy((char*)host_out + (size_t)i * out_ld * es, stage + i * row_bytes, (size_t)e->k * es);
-}
-
-// The first k columns of n kp-wide device rows to host_out, through the pinned staging buffer in as many passes as it
-// takes, the way als_read_factors reads. Waits for the stream.
-int download_rows(als_engine* e, const char* fn, const char* d_rows, int64_t n, void* host_out, int64_t out_ld) {
-    if (int r = ensure_stage(e)) return r;
-    const size_t es = e->elem(), row_bytes = (size_t)e->kp * es;
-    const int64_t rows_per = (int64_t)(e->h_stage.bytes() / row_bytes);
-    for (int64_t r = 0; r < n; r += rows_per) {
-        const int64_t nr = std::min(rows_per, n - r);
-        hipError_t st = cfk::launch_download(d_rows + (size_t)r * row_bytes, e->h_stage.get(), (size_t)nr * row_bytes, e->stream);
-        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-        if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(st));
-        unpack_stage(e, nr, (char*)host_out + (size_t)r * out_ld * es, out_ld);
-    }
-    return ALS_OK;
 }
 
 // One call of als_fold_in or als_solve_implicit.
@@ -130,7 +65,7 @@ int solve_queries(als_engine* e, const QueryCall& c) {
         return fail(ALS_ERR_INVALID_ARGUMENT, "%s: out_ld (%lld) < num_features (%d)", fn, (long long)c.out_ld, e->k);
     if (!implicit && !(c.lambda >= 0.f)) return fail(ALS_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
     int64_t nnz = 0;
-    if (int r = check_queries(fn, n_queries, c.q_ptr, c.q_idx, c.dst_rows, self, opp, &nnz)) return r;
+    if (int r = check_queries(fn, n_queries, c.q_ptr, c.q_idx, c.dst_rows, self.n_rows, opp.n_rows, &nnz)) return r;
     const int64_t p0 = c.q_ptr[0];
     if (implicit)
         for (int64_t q = 0; q < n_queries; ++q)
@@ -147,12 +82,7 @@ int solve_queries(als_engine* e, const QueryCall& c) {
     // longest first (stable), so that the one long query of a training half starts first instead of last. Results do
     // not depend on it.
     std::vector<int64_t> ptr0, order;
-    const int64_t* ptr = c.q_ptr;
-    if (p0 != 0) {
-        ptr0.resize(n_queries + 1);
-        for (int64_t q = 0; q <= n_queries; ++q) ptr0[q] = ptr[q] - p0;
-        ptr = ptr0.data();
-    }
+    const int64_t* ptr = rebase_ptr(c.q_ptr, n_queries, ptr0);
     if (implicit) {
         order.resize(n_queries);
         for (int64_t q = 0; q < n_queries; ++q) order[q] = q;
@@ -164,26 +94,16 @@ int solve_queries(als_engine* e, const QueryCall& c) {
     // workspace, every part 256-byte aligned: ranges, order, indices, ratings, destination rows, the opposite table's
     // Gram and its slabs' tiles, the kp-wide result rows
     const size_t row_bytes = (size_t)e->kp * e->elem();
-    int64_t need = 0;
-    auto part = [&need](bool used, int64_t bytes) {
-        const int64_t off = need;
-        if (used) need += (bytes + 255) / 256 * 256;
-        return off;
-    };
-    const int64_t off_ptr = part(true, (n_queries + 1) * 8);
-    const int64_t off_ord = part(implicit, n_queries * 8);
-    const int64_t off_idx = part(true, nnz * 4);
-    const int64_t off_rat = part(true, nnz * 2);
-    const int64_t off_dst = part(c.dst_rows != nullptr, n_queries * 8);
-    const int64_t off_gram = part(implicit, (int64_t)e->kp * (int64_t)row_bytes);
-    const int64_t off_part = part(implicit, gp.partial_bytes);
-    const int64_t off_out = part(true, n_queries * (int64_t)row_bytes);
-    if ((size_t)need > e->d_rec.size()) {   // grow-only; the stream may still be reading the old one
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        const hipError_t st = e->d_rec.reserve((size_t)need);
-        if (st != hipSuccess)
-            return fail(ALS_ERR_OUT_OF_MEMORY, "%s: device allocation (%zu bytes): %s", fn, (size_t)need, hipGetErrorString(st));
-    }
+    Workspace ws;
+    const int64_t off_ptr = ws.part(true, (n_queries + 1) * 8);
+    const int64_t off_ord = ws.part(implicit, n_queries * 8);
+    const int64_t off_idx = ws.part(true, nnz * 4);
+    const int64_t off_rat = ws.part(true, nnz * 2);
+    const int64_t off_dst = ws.part(c.dst_rows != nullptr, n_queries * 8);
+    const int64_t off_gram = ws.part(implicit, (int64_t)e->kp * (int64_t)row_bytes);
+    const int64_t off_part = ws.part(implicit, gp.partial_bytes);
+    const int64_t off_out = ws.part(true, n_queries * (int64_t)row_bytes);
+    if (int r = reserve_workspace(e, fn, ws.need)) return r;
     // a result that fits the pinned staging buffer is queued behind the kernel, so the call waits for the stream once
     bool one_pass = false;
     if (c.host_out) {
@@ -202,32 +122,26 @@ int solve_queries(als_engine* e, const QueryCall& c) {
     a.f.n_queries = n_queries;
     a.f.k = e->k;
     a.f.lambda = c.lambda;
-    hipError_t st = hipMemcpyAsync(w + off_ptr, ptr, (n_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && nnz > 0)
-        st = hipMemcpyAsync(w + off_idx, c.q_idx + p0, nnz * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && nnz > 0)
-        st = hipMemcpyAsync(w + off_rat, c.q_ratings + p0, nnz * sizeof(int16_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && c.dst_rows)
-        st = hipMemcpyAsync(w + off_dst, c.dst_rows, n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+    StreamChain ch{e};
+    ch.upload(w + off_ptr, ptr, (n_queries + 1) * sizeof(int64_t));
+    if (nnz > 0) {
+        ch.upload(w + off_idx, c.q_idx + p0, nnz * sizeof(int32_t));
+        ch.upload(w + off_rat, c.q_ratings + p0, nnz * sizeof(int16_t));
+    }
+    if (c.dst_rows) ch.upload(w + off_dst, c.dst_rows, n_queries * sizeof(int64_t));
     if (implicit) {
         a.gram = w + off_gram;
         a.order = (const int64_t*)(w + off_ord);
         a.alpha = *c.alpha;
-        if (st == hipSuccess)
-            st = hipMemcpyAsync(w + off_ord, order.data(), n_queries * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+        ch.upload(w + off_ord, order.data(), n_queries * sizeof(int64_t));
         // G of the opposite table, recomputed on every call: no per-engine state that could go stale
-        if (st == hipSuccess)
-            st = cfk::launch_gram_table(e->precision, e->kp, opp.ptr, opp.n_rows, gp, w + off_part, w + off_gram, e->stream);
-        if (st == hipSuccess) st = cfk::launch_implicit(e->precision, e->kp, a, p, e->stream);
-    } else if (st == hipSuccess) {
-        st = cfk::launch_fold_in(e->precision, e->kp, a.f, p, e->stream);
+        ch.run(cfk::launch_gram_table, e->precision, e->kp, opp.ptr, opp.n_rows, gp, w + off_part, w + off_gram);
+        ch.run(cfk::launch_implicit, e->precision, e->kp, a, p);
+    } else {
+        ch.run(cfk::launch_fold_in, e->precision, e->kp, a.f, p);
     }
-    if (st == hipSuccess && one_pass)
-        st = cfk::launch_download(w + off_out, e->h_stage.get(), (size_t)n_queries * row_bytes, e->stream);
-    // the host arrays are pageable: the stream has to pass the copies before this call returns
-    const hipError_t st2 = hipStreamSynchronize(e->stream);
-    if (st == hipSuccess) st = st2;
-    if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(st));
+    if (one_pass) ch.run(cfk::launch_download, w + off_out, e->h_stage.get(), (size_t)n_queries * row_bytes);
+    if (int r = ch.wait(fn)) return r;
     if (one_pass) {
         unpack_stage(e, n_queries, c.host_out, c.out_ld);
     } else if (c.host_out) {
@@ -271,18 +185,16 @@ int als_gram_table(als_engine* e, int side, void* host_out, int64_t out_ld) {
     HIP_TRY(hipSetDevice(e->device));
     if (int r = wait_gathers(e, true, true)) return r;
     // workspace: the kp x kp result, then the slabs' tiles
-    const size_t gram_bytes = ((size_t)e->kp * e->kp * e->elem() + 255) / 256 * 256;
-    const size_t need = gram_bytes + (size_t)p.partial_bytes;
-    if (need > e->d_rec.size()) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        const hipError_t st = e->d_rec.reserve(need);
-        if (st != hipSuccess)
-            return fail(ALS_ERR_OUT_OF_MEMORY, "als_gram_table: device allocation (%zu bytes): %s", need, hipGetErrorString(st));
-    }
+    Workspace ws;
+    const int64_t off_gram = ws.part(true, (int64_t)e->kp * e->kp * (int64_t)e->elem());
+    const int64_t off_part = ws.part(true, p.partial_bytes);
+    if (int r = reserve_workspace(e, "als_gram_table", ws.need)) return r;
     char* w = e->d_rec.get();
-    const hipError_t st = cfk::launch_gram_table(e->precision, e->kp, tab.ptr, tab.n_rows, p, w + gram_bytes, w, e->stream);
+    // one launch and download_rows' own wait, no chain: a failed launch has enqueued nothing to wait for
+    const hipError_t st =
+        cfk::launch_gram_table(e->precision, e->kp, tab.ptr, tab.n_rows, p, w + off_part, w + off_gram, e->stream);
     if (st != hipSuccess) return fail(ALS_ERR_DEVICE, "als_gram_table: %s", hipGetErrorString(st));
-    if (int r = download_rows(e, "als_gram_table", w, e->k, host_out, out_ld)) return r;
+    if (int r = download_rows(e, "als_gram_table", w + off_gram, e->k, host_out, out_ld)) return r;
     return sync_checked(e);
 }
 

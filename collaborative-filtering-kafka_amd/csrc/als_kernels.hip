@@ -6,8 +6,8 @@
 // accumulates the Gram matrix Y^T Y and RHS Y^T r, and -- for FULL / REDUCE tasks -- regularises and solves the
 // k x k system inside the wave, writing one factor row.
 //
-// This file is the one translation unit of every kernel and launcher; its device helpers live in private headers,
-// one concern each, included here in order:
+// One of the library's .hip units: the half-iteration, squared error, predict and the copies (als_build, als_recommend,
+// als_rank, als_foldin and als_implicit hold their own kernels). Device helpers: private headers, one concern each, in order:
 //   als_device.h         vector types, wave_sync, bcast, uni, static_for, opaque, pin, load_task
 //   als_slots.h          partial-slot codec and integrity report (SlotCodec), store_partial, sum_partial_slots
 //   als_lds_solve.h      VALU path: per-wave LDS carve-up and the packed-lower-triangle Cholesky (solve_store)
@@ -38,8 +38,8 @@
 namespace cfk {
 namespace {
 
-// Waves (tasks) per workgroup of the MFMA kernel: 4, or 2 at KP = 128, whose 72 KB of per-wave LDS tiles
-// allow two 2-wave workgroups per CU (one wave per SIMD, which its register use allows anyway).
+// Waves (tasks) per workgroup of the MFMA kernel: WAVES (4) at every KP, KP = 128 with its per-wave LDS tiles
+// included. The one place to change should a KP ever want another count.
 template <int KP>
 constexpr int mfma_waves() { return WAVES; }
 

@@ -248,6 +248,80 @@ def test_exclusions_confined_to_one_segment(excl_case):
     check(eng, S, urows, mrows, 10, csr([np.arange(lo, hi)] * len(urows)))
 
 
+def test_rebased_exclusion_pointers(gpu):
+    """excl_ptr[0] = 3: the ranges index a slice behind three entries the call never reads (invalid positions here).
+    Positions and score bits are those of the same exclusions given from excl_ptr[0] = 0, and numpy's."""
+    eng, U, M = tables(gpu, "f32", 5)
+    rng = np.random.default_rng(12)
+    urows, mrows = query_rows(rng, N_U_TABLE, 3, 0), query_rows(rng, N_M_TABLE, 50, 5)
+    S = java_float_dots(U[urows], M[mrows])
+    top = expected_topn(S, 5)[0]
+    excl = csr([np.unique(np.append(top[0, :2], 49)), [], np.sort(top[2])])             # part of a top 5, none, all of one
+    assert excl[0][0] == 0
+    at3 = (excl[0] + 3, np.concatenate([np.array([-3, 50, 7000], np.int32), excl[1]]))
+    idx0, score0 = eng.recommend(urows, mrows, 5, excl)
+    idx3, score3 = eng.recommend(urows, mrows, 5, at3)
+    assert np.array_equal(idx0, idx3) and np.array_equal(score0.view(np.uint32), score3.view(np.uint32))
+    want_idx, want_score = expected_topn(S, 5, excl)
+    assert np.array_equal(idx3, want_idx) and np.array_equal(score3, want_score)
+    assert not np.array_equal(want_idx, top)                                             # the exclusions took effect
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the workspace every synchronous call shares
+# ---------------------------------------------------------------------------------------------------------------------
+def _a256(n):
+    return (n + 255) // 256 * 256
+
+
+def test_shared_workspace_across_every_call(gpu):
+    """recommend, rank_targets, fold_in, gram_table, solve_implicit and the first recommend again on one engine (k = 16,
+    f32): all five lay their parts out in the one grow-only workspace, each call here needs more of it than the one
+    before (the byte counts below restate the layouts of als_plan.cpp and the calls, every part 256-byte aligned), and
+    every result is bit for bit that of the same call on an engine that has made no other call."""
+    k, row_b = 16, 64
+    rng = np.random.default_rng(13)
+    U = rng.standard_normal((60, k)).astype(np.float32)
+    M = rng.standard_normal((2100, k)).astype(np.float32)               # 9 slabs of 256 rows for the table Gram
+    nu, nc, top_n, nt, nq, nnz = 20, 40, 5, 70, 40, 400
+    urows, mrows = query_rows(rng, 60, nu, 1), query_rows(rng, 2100, nc, 2)
+    excl = csr([np.sort(rng.choice(nc, 6, replace=False)) for _ in range(nu)])
+    targets = csr(np.array_split(rng.integers(0, nc, nt).astype(np.int32), nu))
+    qptr = np.zeros(nq + 1, np.int64)
+    qptr[1:] = np.cumsum(rng.multinomial(nnz, np.ones(nq) / nq))
+    qidx = np.concatenate([rng.choice(2100, c, replace=False) for c in np.diff(qptr)]).astype(np.int32)
+    queries = (qptr, qidx, rng.integers(1, 6, nnz).astype(np.int16))
+    slabs = -(-2100 // 256)
+    excl_b = _a256((nu + 1) * 8) + _a256(len(excl[1]) * 4)
+    need = [
+        _a256(nu * 8) + _a256(nc * 8) + 2 * _a256(nu * top_n * 4) + excl_b,                      # recommend (1 segment)
+        _a256(nt * 8) + 4 * _a256(nt * 4) + _a256(nc * 8) + excl_b,                              # rank_targets
+        _a256((nq + 1) * 8) + _a256(nnz * 4) + _a256(nnz * 2) + _a256(nq * row_b),               # fold_in
+        _a256(k * row_b) + slabs * 256 * 4,                                                      # gram_table
+        _a256((nq + 1) * 8) + _a256(nq * 8) + _a256(nnz * 4) + _a256(nnz * 2) + _a256(k * row_b) + slabs * 256 * 4 +
+        _a256(nq * row_b),                                                                       # solve_implicit
+    ]
+    assert need == sorted(set(need)), need
+    calls = [
+        lambda e: e.recommend(urows, mrows, top_n, excl),
+        lambda e: e.rank_targets(urows, mrows, targets, excl),
+        lambda e: (e.fold_in(SIDE_USER, queries, 0.05),),
+        lambda e: (e.gram_table(SIDE_MOVIE),),
+        lambda e: (e.solve_implicit(SIDE_USER, queries, 0.1, 2.0),),
+    ]
+    shared = make_engine(gpu, k, "f32", U, M)
+    assert shared.recommend_plan(nu, nc, top_n)["segments"] == 1
+    got = [call(shared) for call in calls + calls[:1]]
+    for call, g in zip(calls + calls[:1], got):
+        want = call(make_engine(gpu, k, "f32", U, M))
+        assert len(g) == len(want)
+        for a, b in zip(g, want):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(got[0], got[-1]))
+    assert np.array_equal(got[0][0], expected_topn(java_float_dots(U[urows], M[mrows]), top_n, excl)[0])
+    assert all(np.all(np.isfinite(g[0])) and np.any(g[0] != 0) for g in got[2:5])
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # errors
 # ---------------------------------------------------------------------------------------------------------------------
