@@ -86,6 +86,8 @@ SIGNATURES = [
     ("als_predict", _i, [_vp, _pi64, _i64, _pi64, _i64, _pf]),
     ("als_recommend", _i, [_vp, _pi64, _i64, _pi64, _i64, _i, _pi64, _pi32, _pi32, _pf]),
     ("als_recommend_plan", _i, [_vp, _i64, _i64, _i, _pi64]),
+    ("als_similar", _i, [_vp, _i, _i, _pi64, _i64, _pi64, _i64, _i, _i, _pi32, _pf]),
+    ("als_similar_plan", _i, [_vp, _i64, _i64, _i, _pi64]),
     ("als_rank_targets", _i, [_vp, _pi64, _i64, _pi64, _i64, _pi64, _pi32, _pi64, _pi32, _pf, _pi32]),
     ("als_rank_plan", _i, [_vp, _i64, _i64, _pi64]),
     ("als_fold_in", _i, [_vp, _i, _i64, _pi64, _pi32, _pi16, _f, _pi64, _vp, _i64]),

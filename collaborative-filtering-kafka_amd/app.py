@@ -66,6 +66,18 @@ def seen_exclusions(ds: Dataset, world: int, rank: int, movie_rows) -> tuple[np.
     return rows, excl_ptr, pos[keep].astype(np.int32)
 
 
+def ids_to_slots(ds: Dataset, side: int, world: int, ids) -> np.ndarray:
+    """Factor rows (slots under `world` shards) of the entities of `side` with the given raw ids, in the order given;
+    repeats allowed. Raises ValueError naming the first id that is not in `ds`. Pure host code."""
+    want = np.ascontiguousarray(ids, np.int64).reshape(-1)
+    known = ds.ids(side)                                        # ascending
+    at = np.minimum(np.searchsorted(known, want), max(len(known) - 1, 0))
+    bad = np.nonzero(known[at] != want)[0] if len(known) else np.arange(len(want))
+    if len(bad):
+        raise ValueError(f"unknown {'user' if side == SIDE_USER else 'movie'} id {int(want[bad[0]])}")
+    return ds.slots(side, world)[at].astype(np.int64)
+
+
 def heldout_queries(ds: Dataset, movie_ids, user_ids, world: int, rank: int, movie_rows):
     """What ALSEngine.rank_targets needs to evaluate held-out (movie id, user id) pairs. For rank `rank`'s users in
     shard_user_rows order (ascending raw id): (tgt_ptr, tgt_idx, entry, seen, n_unknown, n_seen).
@@ -406,6 +418,29 @@ class ALSApp:
             user_ids = user_ids[user_ids % self.world == self.rank]
         out = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
         return user_ids, out.astype(np.int64), score
+
+    def _similar(self, side, ids, top_n, metric, exclude_self):
+        all_ids = self.ds.ids(side)
+        cand_rows = self.ds.slots(side, self.world)              # ascending id -> factor row; no spare rows
+        ids = all_ids if ids is None else np.ascontiguousarray(ids, np.int64).reshape(-1)
+        idx, score = self.engine.similar(side, ids_to_slots(self.ds, side, self.world, ids), cand_rows, top_n, metric,
+                                         exclude_self)
+        return ids, np.where(idx >= 0, all_ids[np.maximum(idx, 0)], -1).astype(np.int64), score
+
+    def similar_movies(self, movie_ids=None, top_n: int = 10, metric: str = "cosine",
+                       exclude_self: bool = True) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The top_n nearest movies of the given movies (raw ids; None: every movie, ascending) by the cosine or the dot
+        product of their factor rows (ALSEngine.similar): (ids [n], neighbour_ids [n, top_n], scores [n, top_n]), best
+        first. Candidates are all movies in ascending id, so equal scores go to the smaller id; -1 / -inf where there
+        are fewer than top_n. An unknown id raises ValueError. No collective: after the all-gather every rank holds the
+        whole table and returns the same answer."""
+        return self._similar(SIDE_MOVIE, movie_ids, top_n, metric, exclude_self)
+
+    def similar_users(self, user_ids, top_n: int = 10, metric: str = "cosine",
+                      exclude_self: bool = True) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """similar_movies for users: the nearest users of the given users among all users of the dataset (spare rows are
+        not candidates)."""
+        return self._similar(SIDE_USER, user_ids, top_n, metric, exclude_self)
 
     # ---- implicit feedback (Hu, Koren, Volinsky 2008): single rank --------------------------------------------------
     def _implicit_csr(self, side):

@@ -2,7 +2,7 @@
 //
 //   als_app NUM_PARTITIONS NUM_FEATURES LAMBDA NUM_ITERATIONS dataset NUM_MOVIES NUM_USERS
 //           [--precision f32|f64] [--seed S] [--gpus G] [--out DIR] [--top-n N] [--no-matrix]
-//           [--probe FILE] [--probe-top-n N]
+//           [--probe FILE] [--probe-top-n N] [--similar N]
 //
 // Same 7 positional arguments (README.md:35); the extras are optional trailing flags. The run follows the
 // reference topology (ALSApp.java:52-184) bulk-synchronously: ingest (NetflixDataFormatProducer), in-blocks
@@ -19,6 +19,9 @@
 // --probe FILE evaluates held-out ratings (Netflix format, the training file's loader) after training and prints
 // "probe n=... unknown=... seen=... ranked=... rmse=... mae=... hr@N=... ndcg@N=... mrr=... mpr=..." (als_rank_targets:
 // exact scores and exact ranks against all movies the user has not rated; N = --probe-top-n, 1..64, default 10).
+// --similar N (1..64) writes <out>/similar_<timestamp> after training: per movie, ascending id, its N nearest movies by
+// the cosine of their factor rows, itself excluded, as lines "movieId,neighbourId,score" (als_similar; the writer is
+// the recommendations'). It needs no matrix either.
 // Deviations that turn reference hangs into errors: duplicate (user, movie) pairs, and NUM_MOVIES /
 // NUM_USERS not equal to the rated-entity counts (FeatureCollector.java:43 would never fire).
 #include <sys/stat.h>
@@ -95,7 +98,7 @@ int main(int argc, char** argv) {
     unsigned long long seed = 42;
     int gpus = 0;
     std::string outdir = "./predictions";
-    long long top_n = 0, probe_top_n = 10;
+    long long top_n = 0, probe_top_n = 10, similar_n = 0;
     const char* probe = nullptr;
     bool matrix = true;
     for (int i = 8; i < argc; ++i) {
@@ -121,6 +124,11 @@ int main(int argc, char** argv) {
         } else if (a == "--probe-top-n" && i + 1 < argc) {
             if (!parse_int(argv[++i], 1, 64, probe_top_n)) {
                 fprintf(stderr, "als_app: --probe-top-n 1..64\n");
+                return 1;
+            }
+        } else if (a == "--similar" && i + 1 < argc) {
+            if (!parse_int(argv[++i], 1, 64, similar_n)) {
+                fprintf(stderr, "als_app: --similar 1..64\n");
                 return 1;
             }
         } else if (a == "--no-matrix") {
@@ -226,7 +234,7 @@ int main(int argc, char** argv) {
     if (als_dataset_slots(ds, ALS_SIDE_USER, G, urows.data()) != ALS_OK ||
         als_dataset_slots(ds, ALS_SIDE_MOVIE, G, mrows.data()) != ALS_OK)
         return die("slots");
-    if (matrix || top_n > 0) mkdir(outdir.c_str(), 0755);
+    if (matrix || top_n > 0 || similar_n > 0) mkdir(outdir.c_str(), 0755);
     if (matrix) {
         // FeatureCollector: factors in ascending id order (their slots in engine 0's gathered replicas); U M^T on the
         // GPU with the collector's Java-float dot, then the EJML CSV text on the host.
@@ -266,6 +274,22 @@ int main(int argc, char** argv) {
         if (als_write_recommendations_csv(path.c_str(), uid.data(), nu, (int)top_n, movie.data(), score.data()) != ALS_OK)
             return die("recommendations");
         printf("Recommendations: %s\n", path.c_str());
+    }
+    if (similar_n > 0) {
+        // Queries = candidates = all movies in ascending id: a position is a movie, ties go to the smaller id.
+        std::vector<int64_t> ids(nm);
+        if (als_dataset_ids(ds, ALS_SIDE_MOVIE, ids.data()) != ALS_OK) return die("ids");
+        std::vector<int32_t> idx((size_t)nm * similar_n);
+        std::vector<float> score((size_t)nm * similar_n);
+        if (als_similar(eng[0], ALS_SIDE_MOVIE, ALS_SIM_COSINE, mrows.data(), nm, mrows.data(), nm, (int)similar_n, 1,
+                        idx.data(), score.data()) != ALS_OK)
+            return die("similar");
+        std::vector<int64_t> neighbour((size_t)nm * similar_n);
+        for (size_t i = 0; i < idx.size(); ++i) neighbour[i] = idx[i] >= 0 ? ids[idx[i]] : -1;
+        const std::string path = outdir + "/similar_" + java_timestamp();
+        if (als_write_recommendations_csv(path.c_str(), ids.data(), nm, (int)similar_n, neighbour.data(), score.data()) != ALS_OK)
+            return die("similar csv");
+        printf("Similar movies: %s\n", path.c_str());
     }
     if (probe) {
         // Held-out triples: the users in ascending id are the query users, a triple's target is its movie's position.

@@ -62,6 +62,21 @@ int check_queries(const char* fn, int64_t n_queries, const int64_t* q_ptr, const
     return ALS_OK;
 }
 
+int check_table_rows(const char* fn, const int64_t* query_rows, int64_t n_queries, const int64_t* cand_rows, int64_t n_cand,
+                     int64_t n_rows) {
+    const struct {
+        const char* name;
+        const int64_t* rows;
+        int64_t n;
+    } lists[2] = {{"query_rows", query_rows, n_queries}, {"cand_rows", cand_rows, n_cand}};
+    for (const auto& l : lists)
+        for (int64_t i = 0; i < l.n; ++i)
+            if (l.rows[i] < 0 || l.rows[i] >= n_rows)
+                return fail(ALS_ERR_INVALID_ARGUMENT, "%s: %s[%lld] = %lld is outside [0, %lld)", fn, l.name, (long long)i,
+                            (long long)l.rows[i], (long long)n_rows);
+    return ALS_OK;
+}
+
 const int64_t* rebase_ptr(const int64_t* ptr, int64_t n, std::vector<int64_t>& store) {
     if (ptr[0] == 0) return ptr;
     store.resize((size_t)n + 1);

@@ -1,5 +1,6 @@
-// als_args.h -- the checks of the caller's CSR arrays that the synchronous engine calls share (als_args.cpp): pure
-// host arithmetic with no HIP header, so that tests/host/args_check.cpp runs them under the sanitizers without a GPU.
+// als_args.h -- the checks of the caller's CSR arrays and row lists that the synchronous engine calls share
+// (als_args.cpp): pure host arithmetic with no HIP header, so that tests/host/args_check.cpp and
+// tests/host/similar_args_check.cpp run them under the sanitizers without a GPU.
 // Every check sets als_last_error() and returns the status. Private to csrc/.
 #pragma once
 #include <cstdint>
@@ -21,6 +22,11 @@ int check_exclusions(const char* fn, const int64_t* excl_ptr, const int32_t* exc
 // and given once. *nnz_out = the entry count.
 int check_queries(const char* fn, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx, const int64_t* dst_rows,
                   int64_t self_rows, int64_t opp_rows, int64_t* nnz_out);
+
+// The two row lists of als_similar against the one table they index, O(n_queries + n_cand): every query_rows[i], then
+// every cand_rows[i], inside [0, n_rows). The message names the array, the index and the value.
+int check_table_rows(const char* fn, const int64_t* query_rows, int64_t n_queries, const int64_t* cand_rows, int64_t n_cand,
+                     int64_t n_rows);
 
 // The n + 1 pointers as the device wants them, starting at 0 (it indexes the uploaded slice): `ptr` itself when
 // ptr[0] == 0, else the differences, kept in `store`.

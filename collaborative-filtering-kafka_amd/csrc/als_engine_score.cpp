@@ -1,5 +1,5 @@
-// als_engine_score.cpp -- the calls that score the resident factors: als_predict, als_recommend and als_rank_targets
-// with their *_plan calls. All three are synchronous, on the host path of als_engine_call.h; each keeps its own order
+// als_engine_score.cpp -- the calls that score the resident factors: als_predict, als_recommend, als_similar and
+// als_rank_targets with their *_plan calls. All four are synchronous, on the host path of als_engine_call.h; each keeps its own order
 // of checks.
 #include "als_engine_call.h"
 
@@ -103,6 +103,58 @@ int als_recommend(als_engine* e, const int64_t* user_rows, int64_t n_users, cons
     c.run(cfk::launch_recommend, e->precision, U.ptr, M.ptr, e->kp, e->k, d_u, n_users, d_m, n_movies, top_n, p, d_eptr,
           d_eidx, d_ps, d_pp, d_score, d_idx);
     const size_t ob = (size_t)n_users * (size_t)top_n * 4;
+    c.download(host_idx, d_idx, ob);
+    c.download(host_score, d_score, ob);
+    return c.finish(fn);
+}
+
+int als_similar_plan(const als_engine* e, int64_t n_queries, int64_t n_cand, int top_n, int64_t info[4]) {
+    if (!e || !info) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (n_queries < 0 || n_cand < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "negative counts");
+    if (top_n < 1 || top_n > cfk::REC_MAX_TOP_N)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "top_n must be 1..%d, got %d", cfk::REC_MAX_TOP_N, top_n);
+    const cfk::RecommendPlan p = cfk::similar_plan(n_queries, n_cand, top_n, e->kp, e->cu_count).sweep;
+    return plan_info(info, p.user_tile, p.segments, p.seg_len, p.lds_bytes);
+}
+
+int als_similar(als_engine* e, int side, int metric, const int64_t* query_rows, int64_t n_queries, const int64_t* cand_rows,
+                int64_t n_cand, int top_n, int exclude_self, int32_t* host_idx, float* host_score) {
+    const char* fn = "als_similar";
+    if (int r = check_engine(e)) return r;
+    if (int r = check_side(side)) return r;
+    if (metric != ALS_SIM_COSINE && metric != ALS_SIM_DOT)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_similar: metric must be ALS_SIM_COSINE or ALS_SIM_DOT, got %d", metric);
+    if (n_queries < 0 || n_cand < 0) return fail(ALS_ERR_INVALID_ARGUMENT, "negative counts");
+    if (top_n < 1 || top_n > cfk::REC_MAX_TOP_N)
+        return fail(ALS_ERR_INVALID_ARGUMENT, "als_similar: top_n must be 1..%d, got %d", cfk::REC_MAX_TOP_N, top_n);
+    if (n_cand > INT32_MAX) return fail(ALS_ERR_INVALID_ARGUMENT, "als_similar: n_cand must be below 2^31");
+    const Factors& F = e->fac[side];
+    if (!F.ptr) return fail(ALS_ERR_STATE, "als_similar: factor matrix not allocated/bound");
+    if (n_queries == 0 || n_cand == 0) return ALS_OK;
+    if (!query_rows || !cand_rows || !host_idx || !host_score) return fail(ALS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (int r = check_table_rows(fn, query_rows, n_queries, cand_rows, n_cand, F.n_rows)) return r;
+    const cfk::SimilarPlan p = cfk::similar_plan(n_queries, n_cand, top_n, e->kp, e->cu_count);
+    if (p.sweep.lds_bytes > cfk::REC_LDS_LIMIT) return fail(ALS_ERR_UNSUPPORTED, "als_similar: launch plan exceeds the LDS");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int r = wait_gathers(e, side == ALS_SIDE_MOVIE, side == ALS_SIDE_USER)) return r;
+    if (int r = reserve_workspace(e, fn, p.workspace_bytes)) return r;
+    char* w = e->d_rec.get();
+    int64_t* d_q = (int64_t*)(w + p.sweep.off_urows);
+    int64_t* d_c = (int64_t*)(w + p.sweep.off_mrows);
+    int32_t* d_idx = (int32_t*)(w + p.sweep.off_idx);
+    float* d_score = (float*)(w + p.sweep.off_score);
+    float* d_ps = (float*)(w + p.sweep.off_part_score);
+    int32_t* d_pp = (int32_t*)(w + p.sweep.off_part_pos);
+    const bool cosine = metric == ALS_SIM_COSINE;
+    float* d_inv_q = cosine ? (float*)(w + p.off_inv_q) : nullptr;
+    float* d_inv_c = cosine ? (float*)(w + p.off_inv_c) : nullptr;
+    StreamChain c{e};
+    c.upload(d_q, query_rows, n_queries * sizeof(int64_t));
+    c.upload(d_c, cand_rows, n_cand * sizeof(int64_t));
+    if (cosine) c.run(cfk::launch_similar_norms, e->precision, F.ptr, e->kp, e->k, d_q, n_queries, d_c, n_cand, d_inv_q, d_inv_c);
+    c.run(cfk::launch_similar_sweep, e->precision, F.ptr, e->kp, e->k, d_q, n_queries, d_c, n_cand, top_n, p.sweep, d_inv_q,
+          d_inv_c, exclude_self != 0, d_ps, d_pp, d_score, d_idx);
+    const size_t ob = (size_t)n_queries * (size_t)top_n * 4;
     c.download(host_idx, d_idx, ob);
     c.download(host_score, d_score, ob);
     return c.finish(fn);

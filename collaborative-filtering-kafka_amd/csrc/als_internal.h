@@ -1,5 +1,5 @@
 // Internal declarations shared by the engine (als_engine*.cpp, their state: als_engine_impl.h) and the kernels
-// (als_kernels.hip, als_recommend.hip, als_rank.hip, als_foldin.hip, als_implicit.hip, als_build.hip).
+// (als_kernels.hip, als_recommend.hip, als_similar.hip, als_rank.hip, als_foldin.hip, als_implicit.hip, als_build.hip).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -132,6 +132,16 @@ hipError_t launch_recommend(int precision, const void* U, const void* M, int kp,
                             int64_t n_users, const int64_t* mrows, int64_t n_cand, int top_n,
                             const RecommendPlan& plan, const int64_t* excl_ptr, const int32_t* excl_idx,
                             float* part_score, int32_t* part_pos, float* out_score, int32_t* out_pos, hipStream_t s);
+// Nearest rows of one factor table (als_similar), all arrays on the device. launch_similar_norms (als_similar.hip):
+// inv_q[i] / inv_c[i] = 1 / sqrt(dot of row qrows[i] / crows[i] with itself), 0 for a zero row. launch_similar_sweep
+// (als_recommend.hip): launch_recommend's sweep with both row lists in `table`, every score scaled by the two inverse
+// norms (both NULL: the plain dot), and -- exclude_self -- without the candidate positions that hold the query's slot.
+hipError_t launch_similar_norms(int precision, const void* table, int kp, int k, const int64_t* qrows, int64_t n_queries,
+                                const int64_t* crows, int64_t n_cand, float* inv_q, float* inv_c, hipStream_t s);
+hipError_t launch_similar_sweep(int precision, const void* table, int kp, int k, const int64_t* qrows, int64_t n_queries,
+                                const int64_t* crows, int64_t n_cand, int top_n, const RecommendPlan& plan,
+                                const float* inv_q, const float* inv_c, bool exclude_self, float* part_score,
+                                int32_t* part_pos, float* out_score, int32_t* out_pos, hipStream_t s);
 // Held-out evaluation (als_rank.hip), all arrays on the device. Target entry t = (factor row trow[t] of its user,
 // candidate position tpos[t], query-user index tuser[t]). launch_score_pairs: score[t] = the same dot for the pair.
 // launch_rank: rank[t] = candidates that come before the target under als_recommend's order (tscore = the scores just

@@ -397,6 +397,17 @@ RecommendPlan recommend_plan(int64_t n_users, int64_t n_cand, int top_n, int kp,
     return p;
 }
 
+SimilarPlan similar_plan(int64_t n_queries, int64_t n_cand, int top_n, int kp, int cu_count) {
+    SimilarPlan p;
+    p.sweep = recommend_plan(n_queries, n_cand, top_n, kp, cu_count);
+    auto align = [](int64_t b) { return (b + 255) / 256 * 256; };
+    int64_t off = p.sweep.workspace_bytes;
+    p.off_inv_q = off, off += align(std::max<int64_t>(n_queries, 0) * 4);
+    p.off_inv_c = off, off += align(std::max<int64_t>(n_cand, 0) * 4);
+    p.workspace_bytes = off;
+    return p;
+}
+
 RankPlan rank_plan(int64_t n_targets, int64_t n_cand, int kp, int cu_count) {
     (void)kp;
     RankPlan p;

@@ -184,6 +184,18 @@ struct RecommendPlan {
 // REC_FEAT_CHUNK whatever the row length); it is part of the signature so that a kp-dependent tile can come later.
 RecommendPlan recommend_plan(int64_t n_users, int64_t n_cand, int top_n, int kp, int cu_count);
 
+// ---- nearest rows of one table (als_similar: als_recommend.hip's sweep, als_similar.hip's norms) --------------------
+// The launch shape is recommend_plan's for (n_queries, n_cand, top_n): the sweep is the same kernel with the same LDS.
+// The workspace is that plan's (off_urows = the query rows, off_mrows = the candidate rows) with the two arrays of
+// inverse norms (float per query, float per candidate) after it.
+struct SimilarPlan {
+    RecommendPlan sweep;
+    int64_t off_inv_q = 0, off_inv_c = 0;   // byte offsets, 256-byte aligned
+    int64_t workspace_bytes = 0;            // the sweep's parts and the two arrays
+};
+// Pure function of its arguments.
+SimilarPlan similar_plan(int64_t n_queries, int64_t n_cand, int top_n, int kp, int cu_count);
+
 // ---- held-out evaluation: exact target ranks (als_rank.hip) ---------------------------------------------------------
 // The row dimension of a tile is target entries, not users: a 256-thread workgroup owns RANK_TGT_TILE targets (each with
 // its user's factor row) and sweeps the RANK_CAND_TILE-candidate tiles of one candidate segment with the recommend

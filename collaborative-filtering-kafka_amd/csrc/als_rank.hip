@@ -24,17 +24,7 @@ namespace {
 
 constexpr int TT = score_tile::TR, TC = score_tile::TC, PITCH = score_tile::PITCH;
 using score_tile::better;
-
-// The exact dot of one pair straight from the tables: strictly sequential in feature order.
-template <class T>
-__device__ __forceinline__ float pair_dot(const T* __restrict__ u, const T* __restrict__ m, int k) {
-    float total = 0.f;
-    {
-#pragma clang fp contract(off)
-        for (int f = 0; f < k; ++f) total = total + (float)u[f] * (float)m[f];   // rounded product, rounded sum
-    }
-    return total;
-}
+using score_tile::pair_dot;
 
 // One thread per target entry.
 template <class T>

@@ -5,8 +5,12 @@
 // M[movie_rows[c]], computed tile by tile by als_score_tile.h (shared with als_rank.hip).
 // Order (total): the higher score first, compared as floats (-0 == +0), equal scores by the smaller position c. The
 // result therefore does not depend on tiles, segments or the order in which lanes insert.
+//
+// als_similar is the same sweep under the compile-time policy SIM: both row lists index one
+// table, a cell is scaled by the inverse norms of its two rows (cosine), and the only exclusion is the query's own slot.
 #include <climits>
 #include <cmath>
+#include <type_traits>
 
 #include "als_internal.h"
 #include "als_score_tile.h"
@@ -90,10 +94,20 @@ struct RecArgs {
     int32_t* out_pos;
 };
 
+// als_similar's sweep: U is the one table (M is not read), urows / mrows are the query and candidate slots of it,
+// excl_ptr / excl_idx are not read.
+struct SimArgs : RecArgs {
+    const float* inv_q;   // [n_users] 1 / |query row|, 0 for a zero row; NULL: the plain dot, no scaling
+    const float* inv_c;   // [n_cand] the same per candidate position
+    int exclude_self;     // candidate positions that hold the query's own slot are not eligible
+};
+
 // Workgroup (blockIdx.x, blockIdx.y) = (user tile, candidate segment). Thread (ty, tx) of the 16 x 16 grid owns the
 // cells of users ty + 16 i and candidates tx + 16 j (i, j < 4), scored by score_tile::score.
-template <class T>
-__global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
+// SIM (als_similar) differs in three places, each under if constexpr: the table the candidate rows come from, the
+// scaling of the 16 cells after score_tile::score, and the survivors' exclusion test.
+template <class T, bool SIM>
+__global__ __launch_bounds__(256) void als_recommend_kernel(std::conditional_t<SIM, SimArgs, RecArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float rsm[];
     const int n = a.top_n;
     float* su = rsm;                         // [TU][PITCH]
@@ -114,7 +128,7 @@ __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
     const int64_t seg_begin = (int64_t)blockIdx.y * a.seg_len;
     const int64_t seg_end = min(a.n_cand, seg_begin + a.seg_len);
     const T* U = (const T*)a.U;
-    const T* M = (const T*)a.M;
+    const T* M = SIM ? U : (const T*)a.M;
     const int k = a.k;
 
     for (int i = tid; i < TU * n; i += 256) {
@@ -137,14 +151,26 @@ __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
         const int64_t u = u0 + sr + 8 * r;
         urow[r] = u < a.n_users ? U + a.urows[u] * (int64_t)a.kp : nullptr;
     }
-    // exclusion ranges of this thread's 4 users
-    int64_t ex_lo[4], ex_hi[4];
+    // exclusion ranges of this thread's 4 users; SIM: their own slots (-1: no candidate holds it) and inverse norms
+    int64_t ex_lo[SIM ? 1 : 4], ex_hi[SIM ? 1 : 4], qslot[SIM ? 4 : 1];
+    float qinv[SIM ? 4 : 1];
+    bool scale = false;
+    if constexpr (SIM) {
+        scale = a.inv_q != nullptr;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t u = u0 + ty + 16 * i;
-        const bool has = a.excl_ptr != nullptr && u < a.n_users;
-        ex_lo[i] = has ? a.excl_ptr[u] : 0;
-        ex_hi[i] = has ? a.excl_ptr[u + 1] : 0;
+        for (int i = 0; i < 4; ++i) {
+            const int64_t u = u0 + ty + 16 * i;
+            qslot[i] = a.exclude_self && u < a.n_users ? a.urows[u] : -1;
+            qinv[i] = scale && u < a.n_users ? a.inv_q[u] : 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t u = u0 + ty + 16 * i;
+            const bool has = a.excl_ptr != nullptr && u < a.n_users;
+            ex_lo[i] = has ? a.excl_ptr[u] : 0;
+            ex_hi[i] = has ? a.excl_ptr[u + 1] : 0;
+        }
     }
 
     // merge the queues of this wave's users (wave w: users w, w + 4, ...) into their lists
@@ -175,10 +201,29 @@ __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
             mrow[r] = c < seg_end ? M + a.mrows[c] * (int64_t)a.kp : nullptr;
         }
         float acc[4][4];
-        score_tile::score(acc, su, sm, urow, mrow, k, c0 == seg_begin, tid);
+        if constexpr (SIM) {
+            // the tile's 4 inverse norms are asked for before the dots and used after them
+            float cinv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t c = c0 + tx + 16 * j;
+                cinv[j] = scale && c < seg_end ? a.inv_c[c] : 0.f;
+            }
+            score_tile::score(acc, su, sm, urow, mrow, k, c0 == seg_begin, tid);
+            if (scale) {   // (cell * inv(q)) * inv(c): two rounded products
+#pragma clang fp contract(off)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * qinv[i]) * cinv[j];
+            }
+        } else {
+            score_tile::score(acc, su, sm, urow, mrow, k, c0 == seg_begin, tid);
+        }
 
-        // selection: a cell that does not come before its user's threshold is dropped here; the exclusion list is
-        // consulted only for the survivors, and excluded ones never reach the queue (so they cannot raise the threshold)
+        // selection: a cell that does not come before its user's threshold is dropped here; the exclusion list (SIM:
+        // the candidate's slot) is consulted only for the survivors, and excluded ones never reach the queue (so they
+        // cannot raise the threshold)
         unsigned pend = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -189,9 +234,14 @@ __global__ __launch_bounds__(256) void als_recommend_kernel(RecArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t c = c0 + tx + 16 * j;
-                if (c < seg_end && better(acc[i][j], (int)c, ts, tp) &&
-                    !(ex_hi[i] > ex_lo[i] && excluded(a.excl_idx, ex_lo[i], ex_hi[i], (int)c)))
-                    pend |= 1u << (i * 4 + j);
+                if constexpr (SIM) {
+                    if (c < seg_end && better(acc[i][j], (int)c, ts, tp) && a.mrows[c] != qslot[i])
+                        pend |= 1u << (i * 4 + j);
+                } else {
+                    if (c < seg_end && better(acc[i][j], (int)c, ts, tp) &&
+                        !(ex_hi[i] > ex_lo[i] && excluded(a.excl_idx, ex_lo[i], ex_hi[i], (int)c)))
+                        pend |= 1u << (i * 4 + j);
+                }
             }
         }
         for (;;) {
@@ -278,6 +328,39 @@ __global__ __launch_bounds__(256) void als_recommend_merge(const float* __restri
     }
 }
 
+// Both calls' launch: the scoring kernel over (user tiles, segments), then the merge kernel when there are several
+// segments. A: RecArgs or SimArgs, filled by the caller up to the outputs.
+template <bool SIM, class A>
+hipError_t launch_sweep(int precision, A a, int64_t n_users, int64_t n_cand, int top_n, const RecommendPlan& plan,
+                        float* part_score, int32_t* part_pos, float* out_score, int32_t* out_pos, hipStream_t s) {
+    if (n_users <= 0 || n_cand <= 0) return hipSuccess;
+    if (top_n < 1 || top_n > REC_MAX_TOP_N || n_cand > INT32_MAX || plan.user_tiles > INT32_MAX ||
+        plan.segments < 1 || plan.segments > REC_MAX_SEGMENTS || plan.lds_bytes > REC_LDS_LIMIT)
+        return hipErrorInvalidValue;
+    const bool split = plan.segments > 1;
+    a.n_users = n_users;
+    a.n_cand = n_cand;
+    a.top_n = top_n;
+    a.seg_len = plan.seg_len;
+    a.out_score = split ? part_score : out_score;
+    a.out_pos = split ? part_pos : out_pos;
+    const dim3 grid((unsigned)plan.user_tiles, (unsigned)plan.segments);
+    const void* fn = precision == 0 ? (const void*)als_recommend_kernel<float, SIM>
+                                    : (const void*)als_recommend_kernel<double, SIM>;
+    // top_n = 64 needs more than the 64 KiB a kernel gets by default. Every call sets the same bound (the largest any
+    // top_n needs), so engines of several devices and host threads cannot lower it under one another's launch.
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)recommend_lds_bytes(REC_MAX_TOP_N));
+    if (e != hipSuccess) return e;
+    if (precision == 0) als_recommend_kernel<float, SIM><<<grid, 256, (size_t)plan.lds_bytes, s>>>(a);
+    else als_recommend_kernel<double, SIM><<<grid, 256, (size_t)plan.lds_bytes, s>>>(a);
+    e = hipGetLastError();
+    if (e != hipSuccess || !split) return e;
+    als_recommend_merge<<<(unsigned)((n_users + 3) / 4), 256, 0, s>>>(part_score, part_pos, n_users, plan.segments,
+                                                                     top_n, out_score, out_pos);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_recommend(int precision, const void* U, const void* M, int kp, int k, const int64_t* urows,
@@ -285,40 +368,34 @@ hipError_t launch_recommend(int precision, const void* U, const void* M, int kp,
                             const RecommendPlan& plan, const int64_t* excl_ptr, const int32_t* excl_idx,
                             float* part_score, int32_t* part_pos, float* out_score, int32_t* out_pos,
                             hipStream_t s) {
-    if (n_users <= 0 || n_cand <= 0) return hipSuccess;
-    if (top_n < 1 || top_n > REC_MAX_TOP_N || n_cand > INT32_MAX || plan.user_tiles > INT32_MAX ||
-        plan.segments < 1 || plan.segments > REC_MAX_SEGMENTS || plan.lds_bytes > REC_LDS_LIMIT)
-        return hipErrorInvalidValue;
-    const bool split = plan.segments > 1;
     RecArgs a{};
     a.U = U;
     a.M = M;
     a.kp = kp;
     a.k = k;
     a.urows = urows;
-    a.n_users = n_users;
     a.mrows = mrows;
-    a.n_cand = n_cand;
-    a.top_n = top_n;
-    a.seg_len = plan.seg_len;
     a.excl_ptr = excl_ptr;
     a.excl_idx = excl_idx;
-    a.out_score = split ? part_score : out_score;
-    a.out_pos = split ? part_pos : out_pos;
-    const dim3 grid((unsigned)plan.user_tiles, (unsigned)plan.segments);
-    const void* fn = precision == 0 ? (const void*)als_recommend_kernel<float> : (const void*)als_recommend_kernel<double>;
-    // top_n = 64 needs more than the 64 KiB a kernel gets by default. Every call sets the same bound (the largest any
-    // top_n needs), so engines of several devices and host threads cannot lower it under one another's launch.
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)recommend_lds_bytes(REC_MAX_TOP_N));
-    if (e != hipSuccess) return e;
-    if (precision == 0) als_recommend_kernel<float><<<grid, 256, (size_t)plan.lds_bytes, s>>>(a);
-    else als_recommend_kernel<double><<<grid, 256, (size_t)plan.lds_bytes, s>>>(a);
-    e = hipGetLastError();
-    if (e != hipSuccess || !split) return e;
-    als_recommend_merge<<<(unsigned)((n_users + 3) / 4), 256, 0, s>>>(part_score, part_pos, n_users, plan.segments,
-                                                                     top_n, out_score, out_pos);
-    return hipGetLastError();
+    return launch_sweep<false>(precision, a, n_users, n_cand, top_n, plan, part_score, part_pos, out_score, out_pos, s);
+}
+
+hipError_t launch_similar_sweep(int precision, const void* table, int kp, int k, const int64_t* qrows, int64_t n_queries,
+                                const int64_t* crows, int64_t n_cand, int top_n, const RecommendPlan& plan,
+                                const float* inv_q, const float* inv_c, bool exclude_self, float* part_score,
+                                int32_t* part_pos, float* out_score, int32_t* out_pos, hipStream_t s) {
+    if ((inv_q == nullptr) != (inv_c == nullptr)) return hipErrorInvalidValue;
+    SimArgs a{};
+    a.U = table;
+    a.M = table;
+    a.kp = kp;
+    a.k = k;
+    a.urows = qrows;
+    a.mrows = crows;
+    a.inv_q = inv_q;
+    a.inv_c = inv_c;
+    a.exclude_self = exclude_self ? 1 : 0;
+    return launch_sweep<true>(precision, a, n_queries, n_cand, top_n, plan, part_score, part_pos, out_score, out_pos, s);
 }
 
 }  // namespace cfk

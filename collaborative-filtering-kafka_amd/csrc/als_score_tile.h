@@ -3,7 +3,8 @@
 // Score of (row r, candidate position c) = als_predict's cell: the Java-float dot of a U row and an M row
 // (FeatureCollector.java:90-101, EJML multTransB): fp32, product and partial sum rounded separately, features 0..k-1 in
 // order, f64 factors narrowed to float first. So the loop is VALU with contraction off -- an f32 MFMA rounds once per
-// step -- and runs over the k features, not the padded stride. Private to the two kernel files.
+// step -- and runs over the k features, not the padded stride. als_similar.hip takes the one-pair dot from here for its
+// norms. Private to those kernel files.
 #pragma once
 #include "als_plan.h"
 
@@ -17,6 +18,18 @@ static_assert(RANK_TGT_TILE == TR && RANK_CAND_TILE == TC && RANK_FEAT_CHUNK == 
 
 // (s, p) comes before (ts, tp) in the result order. False whenever s is NaN.
 __device__ __forceinline__ bool better(float s, int p, float ts, int tp) { return s > ts || (s == ts && p < tp); }
+
+// The exact dot of one pair straight from the tables: strictly sequential in feature order (als_score_pairs, and the
+// squared norms of als_similar: pair_dot(r, r, k)).
+template <class T>
+__device__ __forceinline__ float pair_dot(const T* __restrict__ u, const T* __restrict__ m, int k) {
+    float total = 0.f;
+    {
+#pragma clang fp contract(off)
+        for (int f = 0; f < k; ++f) total = total + (float)u[f] * (float)m[f];   // rounded product, rounded sum
+    }
+    return total;
+}
 
 // The 4 x 4 cells of thread (ty, tx) = (tid >> 4, tid & 15) of a 256-thread workgroup: rows ty + 16 i, candidates
 // tx + 16 j (i, j < 4). su [TR][PITCH] and sm [TC][PITCH] are the staged tiles in LDS; the 16 candidate rows a wave

@@ -22,6 +22,7 @@ from . import _lib
 from ._lib import F32, F64, SIDE_MOVIE, SIDE_USER, call, ptr
 
 SIDES = {"movie": SIDE_MOVIE, "user": SIDE_USER}
+SIM_METRICS = {"cosine": 0, "dot": 1}   # ALS_SIM_COSINE, ALS_SIM_DOT
 
 
 def _side(s) -> int:
@@ -463,6 +464,31 @@ class ALSEngine:
         """Launch shape recommend() would choose (als_recommend_plan)."""
         v = (ctypes.c_int64 * 4)()
         call("als_recommend_plan", self._h, int(n_users), int(n_movies), int(top_n), v)
+        return {"user_tile": v[0], "segments": v[1], "segment_len": v[2], "lds_bytes": v[3]}
+
+    def similar(self, side, query_rows, cand_rows, top_n: int, metric: str = "cosine",
+                exclude_self: bool = True) -> tuple[np.ndarray, np.ndarray]:
+        """Per query row the top_n nearest candidate rows of the SAME factor table (als_similar): (idx int32 [n, top_n] =
+        positions in cand_rows, score float32 [n, top_n]), best first, ties toward the smaller position, padded with
+        -1 / -inf. side: "movie" / "user" or SIDE_*; metric: "cosine" or "dot" (predict()'s cell formula on two rows of
+        the table; cosine scales it by the two inverse norms, a zero row scores 0). exclude_self leaves out every
+        candidate position that holds the query's own row."""
+        side = SIDES[side] if isinstance(side, str) else int(side)
+        if metric not in SIM_METRICS:
+            raise ValueError("metric must be 'cosine' or 'dot'")
+        qr = np.ascontiguousarray(query_rows, np.int64)
+        cr = np.ascontiguousarray(cand_rows, np.int64)
+        n = int(top_n)
+        idx = np.full((len(qr), max(n, 0)), -1, np.int32)
+        score = np.full((len(qr), max(n, 0)), -np.inf, np.float32)
+        call("als_similar", self._h, side, SIM_METRICS[metric], ptr(qr, ctypes.c_int64), len(qr), ptr(cr, ctypes.c_int64),
+             len(cr), n, int(bool(exclude_self)), ptr(idx, ctypes.c_int32), ptr(score, ctypes.c_float))
+        return idx, score
+
+    def similar_plan(self, n_queries: int, n_cand: int, top_n: int) -> dict:
+        """Launch shape similar() would choose (als_similar_plan), with recommend_plan's keys."""
+        v = (ctypes.c_int64 * 4)()
+        call("als_similar_plan", self._h, int(n_queries), int(n_cand), int(top_n), v)
         return {"user_tile": v[0], "segments": v[1], "segment_len": v[2], "lds_bytes": v[3]}
 
     def rank_targets(self, user_rows, movie_rows, targets, exclude=None,

@@ -198,6 +198,36 @@ int als_recommend(als_engine* e, const int64_t* user_rows, int64_t n_users, cons
  * lists per segment, merged by a second kernel), [2] = candidates per segment, [3] = dynamic LDS bytes per workgroup. */
 int als_recommend_plan(const als_engine* e, int64_t n_users, int64_t n_movies, int top_n, int64_t info[4]);
 
+/* Nearest rows of ONE factor table (no reference counterpart): "more like this movie", "users like this user". Per query
+ * row the top_n best-scoring candidate rows of the same table, by cosine or by dot product, scored and selected in one
+ * sweep on the GPU like als_recommend; no n_queries x n_cand matrix is written.
+ *  - side: ALS_SIDE_MOVIE or ALS_SIDE_USER, the table both lists index. query_rows / cand_rows: factor rows (slots) of
+ *    it, any order, repeats allowed; n_cand < 2^31.
+ *  - cell(a, b) = als_predict's cell formula on rows a and b of that table: f64 factors narrowed to float first,
+ *    features 0..k-1 in order, every product and every partial sum rounded separately.
+ *  - ALS_SIM_DOT:    score(q, c) = cell(q, c).
+ *    ALS_SIM_COSINE: score(q, c) = (cell(q, c) * inv(q)) * inv(c) with inv(r) = 1.0f / sqrtf(cell(r, r)), and inv(r) = 0
+ *    when cell(r, r) == 0: the square root, the division and the two products are each one correctly rounded fp32
+ *    operation, in that order, never contracted. A zero row therefore scores 0 against everything. Being rounded five
+ *    times, |score| may exceed 1 by a few ulp and a row's score with itself need not be exactly 1.
+ *  - Order and output are als_recommend's: higher score first, compared as floats; equal scores by the smaller
+ *    candidate position; deterministic, independent of tiles and segments. host_idx[q * top_n + j] = candidate position
+ *    (index into cand_rows) of the j-th best, host_score its score; missing entries are -1 / -INFINITY. top_n: 1..64.
+ *  - exclude_self != 0: every candidate position c with cand_rows[c] == query_rows[q] is ineligible for query q (a slot
+ *    listed several times among the candidates is left out at all of its positions), under als_recommend's rule for
+ *    exclusions: such a cell never competes. Another row with equal factors is not "self".
+ *  - NaN or overflowing factors are out of contract (no fault; the order is unspecified).
+ * Synchronous, on the engine's stream, after that side's pending all-gathers. n_queries == 0 or n_cand == 0: ALS_OK,
+ * outputs untouched. Uses als_recommend's grow-only workspace, never a half's partial slots or pre-split table.
+ * ALS_ERR_INVALID_ARGUMENT: bad side, metric or top_n, negative counts, NULL pointers, a row outside [0, rows of the
+ * table) (the message names the array and the index). ALS_ERR_STATE: the side's table is not allocated or bound. */
+enum { ALS_SIM_COSINE = 0, ALS_SIM_DOT = 1 };
+int als_similar(als_engine* e, int side, int metric, const int64_t* query_rows, int64_t n_queries, const int64_t* cand_rows,
+                int64_t n_cand, int top_n, int exclude_self, int32_t* host_idx, float* host_score);
+/* Launch shape als_similar would choose, as als_recommend_plan reports it: info[0] = queries per workgroup tile, [1] =
+ * candidate segments S, [2] = candidates per segment, [3] = dynamic LDS bytes per workgroup. */
+int als_similar_plan(const als_engine* e, int64_t n_queries, int64_t n_cand, int top_n, int64_t info[4]);
+
 /* Held-out evaluation from the resident factors (no reference counterpart): for given (user, candidate) pairs -- the
  * targets -- the exact score and the exact rank of the target among the user's candidates. One candidate sweep on the
  * GPU counts what comes before each target; nothing dense is written and nothing is sorted. The rank gives HR@N,
