@@ -96,6 +96,8 @@ SIGNATURES = [
     ("als_gram_table_plan", _i, [_vp, _i64, _pi64]),
     ("als_solve_implicit", _i, [_vp, _i, _i64, _pi64, _pi32, _pi16, _f, _f, _pi64, _vp, _i64]),
     ("als_solve_implicit_plan", _i, [_vp, _i64, _pi64]),
+    ("als_implicit_objective", _i, [_vp, _i, _i64, _pi64, _pi32, _pi16, _pi64, _f, _f, _pd, _pd]),
+    ("als_implicit_objective_plan", _i, [_vp, _i64, _pi64]),
     ("als_sq_error", _i, [_vp, _i, _pd, _pi64]),
     ("als_synchronize", _i, [_vp]),
     ("als_integrity_status", _i, [_vp, ctypes.POINTER(ctypes.c_uint32), _i]),

@@ -484,6 +484,27 @@ class ALSApp:
         err = (R > 0).astype(np.float64) - U @ M.T
         return float(np.sum((1.0 + alpha * R) * err * err) + self.ALS_LAMBDA * (np.sum(U * U) + np.sum(M * M)))
 
+    def implicit_objective(self, alpha: float) -> dict:
+        """The implicit-feedback loss of the current factors, on the device and without the grid
+        (ALSEngine.implicit_objective over the cached user-side CSR, this app's lambda): {"quad", "observed", "ridge",
+        "ridge_opp", "loss"}, "loss" being implicit_loss()'s number. One pass over the ratings plus k^2 per user; no
+        factors are read back."""
+        row_ptr, col, rat, row_offset, n_rows = self._implicit_csr(SIDE_USER)
+        return self.engine.implicit_objective(SIDE_USER, (row_ptr, col, rat),
+                                              row_offset + np.arange(n_rows, dtype=np.int64), self.ALS_LAMBDA, alpha)
+
+    def implicit_fit(self, alpha: float, max_iterations: int, rel_tol: float = 0.0) -> list[float]:
+        """Implicit-feedback training with a convergence check: the loss before training, then implicit_iteration() and
+        the loss after each iteration, stopping after the first iteration whose drop prev - cur is <= rel_tol * prev (or
+        after max_iterations). Returns the losses, the one before training first."""
+        losses = [self.implicit_objective(alpha)["loss"]]
+        for _ in range(int(max_iterations)):
+            self.implicit_iteration(alpha)
+            losses.append(self.implicit_objective(alpha)["loss"])
+            if losses[-2] - losses[-1] <= rel_tol * losses[-2]:
+                break
+        return losses
+
     def fold_in_implicit(self, users, alpha: float, dst_rows=None) -> np.ndarray:
         """fold_in() under the implicit-feedback model: the users' factors from ALSEngine.solve_implicit against the
         resident movie factors."""

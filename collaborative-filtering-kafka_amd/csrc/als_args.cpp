@@ -62,6 +62,14 @@ int check_queries(const char* fn, int64_t n_queries, const int64_t* q_ptr, const
     return ALS_OK;
 }
 
+int check_query_rows(const char* fn, const int64_t* rows, int64_t n_queries, int64_t self_rows) {
+    for (int64_t q = 0; q < n_queries; ++q)
+        if (rows[q] < 0 || rows[q] >= self_rows)
+            return fail(ALS_ERR_INVALID_ARGUMENT, "%s: rows[%lld] = %lld of query %lld is outside [0, %lld)", fn, (long long)q,
+                        (long long)rows[q], (long long)q, (long long)self_rows);
+    return ALS_OK;
+}
+
 int check_table_rows(const char* fn, const int64_t* query_rows, int64_t n_queries, const int64_t* cand_rows, int64_t n_cand,
                      int64_t n_rows) {
     const struct {

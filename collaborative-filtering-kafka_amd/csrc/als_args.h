@@ -23,6 +23,10 @@ int check_exclusions(const char* fn, const int64_t* excl_ptr, const int32_t* exc
 int check_queries(const char* fn, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx, const int64_t* dst_rows,
                   int64_t self_rows, int64_t opp_rows, int64_t* nnz_out);
 
+// The factor rows als_implicit_objective reads its x from, one per query, O(n_queries): every rows[q] inside
+// [0, self_rows). A row may be listed twice (nothing is written). The message names the query and the value.
+int check_query_rows(const char* fn, const int64_t* rows, int64_t n_queries, int64_t self_rows);
+
 // The two row lists of als_similar against the one table they index, O(n_queries + n_cand): every query_rows[i], then
 // every cand_rows[i], inside [0, n_rows). The message names the array, the index and the value.
 int check_table_rows(const char* fn, const int64_t* query_rows, int64_t n_queries, const int64_t* cand_rows, int64_t n_cand,

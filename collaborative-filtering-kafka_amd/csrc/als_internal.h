@@ -1,5 +1,5 @@
 // Internal declarations shared by the engine (als_engine*.cpp, their state: als_engine_impl.h) and the kernels
-// (als_kernels.hip, als_recommend.hip, als_similar.hip, als_rank.hip, als_foldin.hip, als_implicit.hip, als_build.hip).
+// (als_kernels.hip, als_recommend.hip, als_similar.hip, als_rank.hip, als_foldin.hip, als_implicit.hip, als_objective.hip, als_build.hip).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -185,6 +185,25 @@ struct ImplicitArgs {
     float alpha;
 };
 hipError_t launch_implicit(int precision, int kp, const ImplicitArgs& a, const FoldinPlan& plan, hipStream_t s);
+// The implicit-feedback objective (als_objective.hip), all arrays on the device, q_ptr / q_idx / q_rat / order as in
+// ImplicitArgs: parts[q] = {x^T G x, sum_e [(1 + alpha r_e)(p_e - y_e . x)^2 - (y_e . x)^2], lambda x^T x} for x = row
+// rows[q] of `self`, in double, and parts[n_queries][0] = lambda tr(G); both over the k true features. The geometry is
+// objective_plan's (als_plan.h). Nothing but `parts` is written.
+struct ObjectiveArgs {
+    const void* opp;          // opposite factor matrix [n_opp][kp], the plain table
+    const void* self;         // this side's factor matrix: the rows x are read from
+    const void* gram;         // [kp][kp], launch_gram_table's
+    const int64_t* q_ptr;     // [n_queries + 1]
+    const int32_t* q_idx;
+    const int16_t* q_rat;
+    const int64_t* rows;      // [n_queries]: factor row of `self` per query (repeats allowed)
+    const int64_t* order;     // [n_queries]: a permutation of the queries
+    double* parts;            // [3 n_queries + 1]
+    int64_t n_queries;
+    int32_t k;
+    float lambda, alpha;
+};
+hipError_t launch_objective(int precision, int kp, const ObjectiveArgs& a, const ObjectivePlan& plan, hipStream_t s);
 hipError_t launch_sq_error(int precision, int kp, const SqErrArgs& a, hipStream_t s);
 // Per-lane accumulator words (elements of the engine precision) of one partial slot: nacc * 64.
 int partial_words_per_lane(int precision, int kp, Path path);

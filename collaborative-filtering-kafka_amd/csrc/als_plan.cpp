@@ -462,4 +462,12 @@ GramTablePlan gram_table_plan(int kp, int elem_bytes, int64_t n_rows, int cu_cou
     return p;
 }
 
+ObjectivePlan objective_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count) {
+    (void)elem_bytes;
+    ObjectivePlan p;
+    p.lds_bytes = objective_lds_bytes(kp);
+    p.grid = std::max<int64_t>(1, std::min<int64_t>(n_queries, (int64_t)OBJECTIVE_WG_PER_CU * std::max(1, cu_count)));
+    return p;
+}
+
 }  // namespace cfk

@@ -286,4 +286,27 @@ inline FoldinPlan implicit_plan(int kp, int elem_bytes, int64_t n_queries, int c
     return foldin_plan(kp, elem_bytes, n_queries, cu_count);
 }
 
+// ---- implicit feedback: the loss without the grid (als_objective.hip) -----------------------------------------------
+// One OBJECTIVE_THREADS workgroup owns one whole query, grid-stride over the queries. Its dynamic LDS is double in both
+// precisions: x (kp doubles), then the waves' three sums (OBJECTIVE_RED_SLOTS doubles: [wave][3], rounded up so that the
+// byte count stays a multiple of 16). The entries are dealt over groups of objective_group_lanes lanes: the 16-byte
+// pieces of a row, rounded up to a power of two (the fp64 strides 80, 96 and 112 have 40, 48 and 56 pieces: 64 lanes).
+constexpr int OBJECTIVE_THREADS = 256;
+constexpr int OBJECTIVE_RED_SLOTS = 16;
+constexpr int OBJECTIVE_WG_PER_CU = 5;   // als_objective_kernel's occupancy: 86 / 90 VGPRs, 5 waves per SIMD
+CFK_HOST_DEVICE constexpr int objective_group_lanes(int kp, int elem_bytes) {
+    int lanes = 1;
+    while (lanes * 16 < kp * elem_bytes) lanes *= 2;
+    return lanes;
+}
+CFK_HOST_DEVICE constexpr int64_t objective_lds_bytes(int kp) { return 8 * (int64_t)(kp + OBJECTIVE_RED_SLOTS); }
+struct ObjectivePlan {
+    int threads = OBJECTIVE_THREADS;
+    int64_t grid = 1;        // workgroups launched: OBJECTIVE_WG_PER_CU per compute unit, never more than the queries
+    int64_t lds_bytes = 0;   // dynamic LDS of one workgroup
+};
+// Pure function of its arguments; kp as in foldin_plan. elem_bytes does not enter the LDS (x is staged as double); it is
+// part of the signature because the group width depends on it. A query's result does not depend on the grid.
+ObjectivePlan objective_plan(int kp, int elem_bytes, int64_t n_queries, int cu_count);
+
 }  // namespace cfk

@@ -585,6 +585,33 @@ class ALSEngine:
         call("als_solve_implicit_plan", self._h, int(n_queries), v)
         return {"threads": v[0], "workgroups": v[1], "batch": v[2], "lds_bytes": v[3]}
 
+    def implicit_objective(self, side, queries, rows, lam: float, alpha: float, parts: bool = False) -> dict:
+        """The implicit-feedback loss of resident factor rows without the dense grid (als_implicit_objective). queries
+        as in solve_implicit(); rows[q] = the factor row of `side` that holds query q's x (repeats allowed). Per query
+        f(x) = x^T G x + sum_e [(1 + alpha r_e)(p_e - y_e . x)^2 - (y_e . x)^2] + lam x^T x, the function solve_implicit()
+        minimises. Returns {"quad", "observed", "ridge"}: the three terms summed over the queries, "ridge_opp": lam tr(G)
+        of the opposite table, "loss": their sum -- the loss over the full grid when the queries are all rows of `side`
+        -- and with parts=True "parts": float64 [n, 3], the terms per query. All in double on the device."""
+        n, qp, qi, qr, rr = _query_arrays(queries, rows)
+        if rr is None:
+            raise ValueError("rows must have one entry per query")
+        out = np.zeros((n, 3), np.float64) if parts else None
+        tot = (ctypes.c_double * 4)()
+        call("als_implicit_objective", self._h, _side(side), n, ptr(qp, ctypes.c_int64), ptr(qi, ctypes.c_int32),
+             ptr(qr, ctypes.c_int16), ptr(rr, ctypes.c_int64), float(np.float32(lam)), float(np.float32(alpha)),
+             ptr(out, ctypes.c_double) if out is not None and n > 0 else None, tot)
+        res = {"quad": tot[0], "observed": tot[1], "ridge": tot[2], "ridge_opp": tot[3],
+               "loss": tot[0] + tot[1] + tot[2] + tot[3]}
+        if parts:
+            res["parts"] = out
+        return res
+
+    def implicit_objective_plan(self, n_queries: int) -> dict:
+        """Launch shape implicit_objective() would choose (als_implicit_objective_plan)."""
+        v = (ctypes.c_int64 * 4)()
+        call("als_implicit_objective_plan", self._h, int(n_queries), v)
+        return {"threads": v[0], "workgroups": v[1], "lds_bytes": v[3]}
+
     def sq_error(self, side="movie"):
         se = ctypes.c_double()
         cnt = ctypes.c_int64()

@@ -334,6 +334,34 @@ int als_solve_implicit(als_engine* e, int side, int64_t n_queries, const int64_t
                        int64_t out_ld);
 /* Launch shape als_solve_implicit would choose: info[] as in als_fold_in_plan. */
 int als_solve_implicit_plan(const als_engine* e, int64_t n_queries, int64_t info[4]);
+/* als_implicit_objective: the implicit-feedback loss of resident factor rows, without the dense grid. For query q, x =
+ * factor row rows[q] of `side`, entries (y_e, r_e) as in als_solve_implicit, G the opposite table's Gram:
+ *     f(x) = x^T G x  +  sum_e [ (1 + alpha r_e)(p_e - s_e)^2 - s_e^2 ]  +  lambda x^T x,    s_e = y_e . x,  p_e = [r_e > 0]
+ * which is x^T A x - 2 b^T x + sum_{r_e > 0} (1 + alpha r_e) with the A and b of als_solve_implicit: the function whose
+ * minimiser that call returns, duplicate entries included. The sum of f over all rows of `side`, plus lambda tr(G), is
+ * the loss sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2) over the full grid.
+ *  - q_ptr, q_idx, q_ratings: exactly als_solve_implicit's, with the same checks (ratings >= 0, lambda and alpha positive
+ *    and finite; every message names the query). rows[q] is required and names a row of `side` in [0, n_total_rows); a
+ *    row may be listed twice. Nothing is written to either factor table.
+ *  - host_parts (NULL, or [n_queries][3] doubles): {x^T G x, sum_e [...], lambda x^T x} per query, the quadratic form and
+ *    the ridge over the num_features true features. A query without entries has a middle part of exactly 0; an entry with
+ *    r_e = 0 contributes exactly 0; a repeated index counts twice.
+ *  - totals[0..2]: the column sums over the queries in ascending query order, summed on the host in double.
+ *    totals[3] = lambda tr(G) over the true features, G bit for bit what als_gram_table returns for the opposite side
+ *    (recomputed on every call: no per-engine state). totals[0] + [1] + [2] + [3] is the loss over the grid when the
+ *    queries are all rows of `side`.
+ *  - All device arithmetic after the loads is double in both precisions, in one fixed order without atomics: a query's
+ *    three doubles are bitwise repeatable and depend on its entries, x, G, lambda and alpha only.
+ *  - n_queries == 0: ALS_OK, totals all zero, no launch. Factor stride > 128: ALS_ERR_UNSUPPORTED. Either factor table
+ *    not allocated/bound: ALS_ERR_STATE.
+ * Synchronous, on the engine's stream, after pending all-gathers of both sides. Uses als_recommend's grow-only workspace
+ * only: a call between two chunks of an explicit half leaves that half bitwise unchanged. */
+int als_implicit_objective(als_engine* e, int side, int64_t n_queries, const int64_t* q_ptr, const int32_t* q_idx,
+                           const int16_t* q_ratings, const int64_t* rows, float lambda, float alpha, double* host_parts,
+                           double totals[4]);
+/* Launch shape als_implicit_objective would choose: info[0] = threads per workgroup, [1] = workgroups launched, [2] = 0,
+ * [3] = dynamic LDS bytes per workgroup. */
+int als_implicit_objective_plan(const als_engine* e, int64_t n_queries, int64_t info[4]);
 
 /* Sum of (r - x_row . y_col)^2 over the block's observed ratings and their count (the RMSE/MSE
  * reduction of scripts/calculate_mse.py:78-90 computed on the device from the factors). Synchronous. */
