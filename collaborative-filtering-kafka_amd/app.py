@@ -255,12 +255,17 @@ class ALSApp:
             n_chunks = [mc, self.overlap_chunks]
         ds.set_slot_chunks(SIDE_USER, n_chunks[SIDE_USER])
         ds.set_slot_chunks(SIDE_MOVIE, n_chunks[SIDE_MOVIE])
-        if engine_factory is None:
-            torch.cuda.set_device(self.device)
-            eng = ALSEngine(self.NUM_FEATURES, self.precision, self.device)
-        else:
-            eng = engine_factory(self.NUM_FEATURES, self.precision, self.device)
-        eng.use_torch_stream()
+        def new_engine():
+            if engine_factory is None:
+                torch.cuda.set_device(self.device)
+                eng = ALSEngine(self.NUM_FEATURES, self.precision, self.device)
+            else:
+                eng = engine_factory(self.NUM_FEATURES, self.precision, self.device)
+            eng.use_torch_stream()
+            return eng
+        self._new_engine = new_engine
+        self._by_id_engine = None
+        eng = new_engine()
         self.spare_user_rows = max(0, int(spare_user_rows))
         spare = [0, self.spare_user_rows]                   # per side: rows after the shard slots
         for side in (SIDE_MOVIE, SIDE_USER):
@@ -505,12 +510,41 @@ class ALSApp:
                 break
         return losses
 
+    def _solve_implicit_users(self, queries, alpha: float, dst_rows, return_host: bool):
+        """ALSEngine.solve_implicit for user queries (q_ptr, q_idx = movie factor rows under self.world, ratings).
+
+        One rank: the engine's own movie table, whose rows are in ascending id. Sharded: the solve adds the Gram of the
+        WHOLE movie table, which als_gram_table sums in table-row order, so on the chunk-major replica the result would
+        depend on the layout in its last bits (and read the padding slots). The movies are therefore gathered in
+        ascending id into the table of a second engine, kept for this purpose, which shares this engine's user table
+        (dst_rows land in the same spare rows): the rows are bit for bit those of a one-rank app with the same factors.
+        One gather of the movie table per call."""
+        q_ptr, q_idx, q_rat = queries
+        if self.world == 1:
+            return self.engine.solve_implicit(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, alpha,
+                                              dst_rows=dst_rows, return_host=return_host)
+        movie_rows = self.ds.slots(SIDE_MOVIE, self.world)       # ascending id -> factor row
+        if getattr(self, "_by_id_engine", None) is None:
+            eng = self._new_engine()
+            eng.alloc_factors(SIDE_MOVIE, len(movie_rows))
+            eng.bind_factors(SIDE_USER, self.engine.factors[SIDE_USER])
+            self._by_id_engine = eng
+        eng = self._by_id_engine
+        self.engine.synchronize()                                  # pending exchanges of the replica included
+        table = self.engine.factors[SIDE_MOVIE]
+        rows = torch.as_tensor(movie_rows, dtype=torch.int64, device=table.device)
+        eng.factors[SIDE_MOVIE][:len(movie_rows)].copy_(table.index_select(0, rows))
+        by_id = np.full(self.info[SIDE_MOVIE]["n_slots"], -1, np.int64)
+        by_id[movie_rows] = np.arange(len(movie_rows), dtype=np.int64)
+        return eng.solve_implicit(SIDE_USER, (q_ptr, by_id[np.asarray(q_idx, np.int64)], q_rat), self.ALS_LAMBDA, alpha,
+                                  dst_rows=dst_rows, return_host=return_host)
+
     def fold_in_implicit(self, users, alpha: float, dst_rows=None) -> np.ndarray:
         """fold_in() under the implicit-feedback model: the users' factors from ALSEngine.solve_implicit against the
-        resident movie factors."""
+        resident movie factors; the same bits whatever the number of ranks (_solve_implicit_users)."""
         movie_rows = self.ds.slots(SIDE_MOVIE, self.world)
         q_ptr, q_idx, q_rat, _, _, _ = foldin_queries(self.ds, self.world, movie_rows, users)
-        return self.engine.solve_implicit(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, alpha, dst_rows=dst_rows)
+        return self._solve_implicit_users((q_ptr, q_idx, q_rat), alpha, dst_rows, True)
 
     def fold_in(self, users, dst_rows=None) -> np.ndarray:
         """User factors [n, k] of users that are not in the training data, from their (movie id, rating) lists and the
@@ -542,8 +576,7 @@ class ALSApp:
             if implicit_alpha is None:
                 self.engine.fold_in(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, dst_rows=rows, return_host=False)
             else:
-                self.engine.solve_implicit(SIDE_USER, (q_ptr, q_idx, q_rat), self.ALS_LAMBDA, implicit_alpha,
-                                           dst_rows=rows, return_host=False)
+                self._solve_implicit_users((q_ptr, q_idx, q_rat), implicit_alpha, rows, False)
             idx, sc = self.engine.recommend(rows, movie_rows, top_n, (excl_ptr, excl_idx) if exclude_seen else None)
             out[u0:u0 + len(part)] = np.where(idx >= 0, movie_ids[np.maximum(idx, 0)], -1)
             score[u0:u0 + len(part)] = sc
